@@ -13,8 +13,16 @@ inputs resident in HBM.  With N > 1 GPUs the image is partitioned into bands of 
 per rank, Gaussians replicated) and the 7-float pose gradient is all-reduced over RCCL each step (strong
 scaling: the total work is fixed).
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel, timed live with HIP events on the
-stream it runs on (vtgs_profile_*); `cpu_baseline` is the float32 oracle on a bounded band of the same scene.
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and no more: scene set-up, clock ramp,
+--warmup steps, --steps timed steps (`ms_per_step`, `value`), the --dump-outputs files if asked for, the line.
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
+    python bench.py ... --dump-outputs DIR    # DIR/<name>.npy: what the last timed step returned (same inputs every run)
+
+--full adds every other measurement and check to the line: the cold first region, per-step event percentiles,
+the tracking / mapping steps, `roofline` for the dominant kernel, timed live with HIP events on the stream it runs
+on (vtgs_profile_*), `cpu_baseline` (the float32 oracle on a bounded band of the same scene), the audited float64
+`parity` block and the `slam` block.
 """
 import argparse
 import json
@@ -75,6 +83,43 @@ def kernel_algorithmic_bytes(n, p, r16, grad_bytes=68):
     }
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(dirname, images, per_gaussian, n):
+    """--dump-outputs: the arrays a caller of the timed step holds after it, as <dirname>/<name>.npy in float32.  `images` end in
+    (H, W), `per_gaussian` arrays (radii, the gradients; saved as radii.npy / grad_<input>.npy) have n rows.  Whole arrays while
+    they fit the budget; beyond it the images keep a fixed, seeded sample of pixels (at most half the budget) and the
+    per-Gaussian arrays the same fixed, seeded sample of rows each, in ascending order."""
+    import numpy as np
+
+    def pick(items, bytes_per_item, budget, seed):
+        keep = int(budget // max(bytes_per_item, 1))
+        if keep >= items:
+            return None
+        return torch.randperm(items, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+
+    os.makedirs(dirname, exist_ok=True)
+    images = {k: v.detach().float().cpu() for k, v in images.items() if v is not None}
+    rows = {k: v.detach().float().cpu() for k, v in per_gaussian.items() if v is not None}
+    out = {}
+    img_bytes = sum(4 * v.numel() for v in images.values())
+    pixels = next(iter(images.values())).shape[-2:].numel() if images else 0
+    pix = pick(pixels, img_bytes // max(pixels, 1), min(img_bytes, DUMP_BUDGET_BYTES // 2), 11) if images else None
+    for k, v in images.items():
+        out[k] = v if pix is None else v.reshape(-1, pixels)[:, pix]
+    left = DUMP_BUDGET_BYTES - sum(4 * v.numel() for v in out.values())
+    sel = pick(n, sum(4 * v.numel() // n for v in rows.values()), left, 12)
+    for k, v in rows.items():
+        out[k] = v if sel is None else v[sel]
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v.numpy(), dtype=np.float32))
+    print(f"[bench] outputs of the last timed step: {sorted(out)} -> {dirname} "
+          f"({sum(4 * v.numel() for v in out.values()) / 1e6:.1f} MB" +
+          ("" if sel is None else f", {sel.numel()} of {n} Gaussians") + ("" if pix is None else f", {pix.numel()} of {pixels} pixels") + ")",
+          file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -108,7 +153,17 @@ def main():
                          "collectives (per-rank kernel times and the replicated share; tools/band_rehearsal.sh)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                                                       "the multi-rank path with all ranks on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, also measure and check everything else the line can carry: the cold first "
+                         "region, per-step hipEvent percentiles, the tracking / mapping steps, per-kernel times + roofline, the CPU "
+                         "baseline, the audited float64 parity block, the SLAM block and (N > 1) the per-rank record.  Without it "
+                         "the run sets up, ramps the clocks, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the LAST timed step returned to its caller -- color, radii, depth and the "
+                         "gradient of every input the mode asks for -- as DIR/<name>.npy (float32; at most 64 MB in all: beyond that "
+                         "the per-Gaussian arrays keep a fixed, seeded sample of rows)")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -185,7 +240,7 @@ def main():
             # same work as one GPU, split by tile rows); the collective is the one north_star names -- the pose gradient
             pose = pose7_reduce(leaves["means3D"], leaves["means3D"].grad)
             all_reduce_sum(pose)
-        return color
+        return color, radii, depth
 
     def fence():
         if dist is not None:
@@ -202,20 +257,28 @@ def main():
     # metric is about is reached first.  (This, not a kernel, is most of the 0.3985 -> 0.36x ms between BENCH_r04 and now.)
     # The region the driver's flags describe, taken the way rounds 1-4 took it -- --warmup steps, then --steps steps, right
     # after the scene set-up, before any ramp -- and reported as `first_region_ms_per_step`, so that the series BENCH_r01..r04
-    # (which recorded THIS number as ms_per_step) stays comparable with the steady-state value of round 5 on
-    for _ in range(args.warmup):
+    # (which recorded THIS number as ms_per_step) stays comparable with the steady-state value of round 5 on.
+    # A second measurement of its own: --full only.
+    first_region_ms = None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        first_dt = time.perf_counter() - t0
+        if dist is not None:
+            tmax = torch.tensor([first_dt], dtype=torch.float64, device=dev)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            first_dt = float(tmax.item())
+        first_region_ms = first_dt / args.steps * 1e3
+    else:
+        # the first call of a process pays ~0.2 s of first-touch costs (code objects, allocator blocks): taken here, as the first
+        # region takes it under --full, so that the ramp below is the same 250 ms of steady steps in both kinds of run
         step()
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    first_dt = time.perf_counter() - t0
-    if dist is not None:
-        tmax = torch.tensor([first_dt], dtype=torch.float64, device=dev)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        first_dt = float(tmax.item())
-    first_region_ms = first_dt / args.steps * 1e3
+        fence()
     ramp_steps, ramp_t0 = 0, time.perf_counter()
     if dist is not None:                       # N ranks: a step holds a collective, so every rank takes the SAME number of steps
         for _ in range(int(args.ramp_ms * 2)):
@@ -243,8 +306,9 @@ def main():
         step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()                              # (what the caller receives from the last timed step: --dump-outputs)
     fence()
     dt = time.perf_counter() - t0
     if dist is not None:
@@ -255,6 +319,45 @@ def main():
     if rank == 0:
         print(f"[bench] timed region done: {ms_per_step:.3f} ms/step", file=sys.stderr, flush=True)
     value = N * P / (dt / args.steps) / 1e6
+    if args.dump_outputs and rank == 0:
+        per_gaussian = {"radii": last[1]}
+        per_gaussian.update({"grad_" + k: leaves[k].grad for k in scene if k in wanted})
+        dump_outputs(args.dump_outputs, {"color": last[0], "depth": last[2]}, per_gaussian, N)
+        del per_gaussian
+    del last
+    info = dgr.last_forward_info()
+
+    def headline(info):
+        return {
+            "metric": "Mgaussians*pixels/s rasterize fwd+bwd", "value": round(value, 1), "unit": "Mgaussians*pixels/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"view-tied synthetic scene (SURVEY 8d), N={N} isotropic Gaussians, {W}x{H}, "
+                                   f"3-channel render, " + {"rasterize": "grads to all six inputs",
+                                                             "tracking": "tracking step: grads to means3D + means2D (Gaussians "
+                                                                         "detached), 7-float pose reduction",
+                                                             "mapping": "mapping step: grads to colours, opacities, scales, "
+                                                                        "means2D"}[mode],
+                       "mode": mode,
+                       "gaussians": N, "width": W, "height": H, "instances_8x8": info["instances"],
+                       "tiles16_touched_R": info["tiles16_touched"], "max_tile_list": info["max_tile_list"],
+                       "partition": "none" if tile_rows is None else f"tile-row bands x{emulated[1] if emulated else world} + " +
+                                    ("all-reduce(28 B per Gaussian)" if mode == "mapping" else "all-reduce(7 floats)")},
+            "clock_ramp": {"untimed_steps_before_warmup": ramp_steps, "ms": args.ramp_ms,
+                           "why": "the GPU idles during scene set-up and its clocks need ~25 ms of work to recover: without this, 20 timed steps "
+                                  "after 5 warm-ups run ~10 % slower than every later region of the same process (0.411 vs 0.369 ms); "
+                                  "on one GPU the untimed steps then continue in chunks of 20 until two chunks agree within 3 % (<= 2 s): "
+                                  "the first process on a fresh box keeps paying first-touch costs for longer"},
+            "libvtgs_sha256": dgr.library_sha256(),
+        }
+
+    if not args.full:
+        # the plain run ends here: set-up, clock ramp, warm-up, the timed steps, the dump, the line
+        if rank == 0:
+            print(json.dumps(dict(headline(info), full=False)))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     def event_steps(fn, k):
         """HIP events on the op's stream around every one of k steps -> per-step ms (the record of an event is a
@@ -501,39 +604,21 @@ def main():
                           "percentile of |d| / (|ref| + 1e-3 max|ref|), max_rel = max|d| / max|ref|"}
 
     if rank == 0:
-        out = {
-            "metric": "Mgaussians*pixels/s rasterize fwd+bwd", "value": round(value, 1), "unit": "Mgaussians*pixels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"view-tied synthetic scene (SURVEY 8d), N={N} isotropic Gaussians, {W}x{H}, "
-                                   f"3-channel render, " + {"rasterize": "grads to all six inputs",
-                                                             "tracking": "tracking step: grads to means3D + means2D (Gaussians "
-                                                                         "detached), 7-float pose reduction",
-                                                             "mapping": "mapping step: grads to colours, opacities, scales, "
-                                                                        "means2D"}[mode],
-                       "mode": mode,
-                       "gaussians": N, "width": W, "height": H, "instances_8x8": info["instances"],
-                       "tiles16_touched_R": r16, "max_tile_list": info["max_tile_list"],
-                       "partition": "none" if tile_rows is None else f"tile-row bands x{emulated[1] if emulated else world} + " +
-                                    ("all-reduce(28 B per Gaussian)" if mode == "mapping" else "all-reduce(7 floats)")},
+        out = headline(info)
+        out.update({
+            "full": True,
             "roofline": roofline, "cpu_baseline": cpu_baseline, "parity": parity, "slam": None, "loop_steps": loop_steps or None,
             "step_events": step_events,
-            "clock_ramp": {"untimed_steps_before_warmup": ramp_steps, "ms": args.ramp_ms,
-                           "why": "the GPU idles during scene set-up and its clocks need ~25 ms of work to recover: without this, 20 timed steps "
-                                  "after 5 warm-ups run ~10 % slower than every later region of the same process (0.411 vs 0.369 ms); "
-                                  "on one GPU the untimed steps then continue in chunks of 20 until two chunks agree within 3 % (<= 2 s): "
-                                  "the first process on a fresh box keeps paying first-touch costs for longer"},
             "kernels_us": {k: round(v["avg_us"], 2) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["avg_us"])},
             "kernels_us_note": {"event_bracket_us": round(bracket_us, 2),
                                 "raw_us": {k: round(v["raw_us"], 2) for k, v in kern.items()},
                                 "what": "kernels_us = HIP-event bracket around each launch minus the measured cost of an empty bracket "
                                         "(two event records back to back, one per forward of the profiled steps); raw_us = the brackets as read"},
-            "libvtgs_sha256": dgr.library_sha256(),
             "first_region_ms_per_step": round(first_region_ms, 4),
             "first_region_note": "--warmup steps then --steps steps right after the scene set-up, BEFORE the clock ramp: the region "
                                  "BENCH_r01..r04 recorded as ms_per_step (cold clocks, first-touch costs); ms_per_step / value are the "
                                  "steady state after `clock_ramp`",
-        }
+        })
         if tile_rows is not None and kern:
             # what every rank of the partition does over ALL Gaussians (projection, per-Gaussian gradient gather) beside what
             # it does for its band only (the two composites): SURVEY 8e "replicated work"

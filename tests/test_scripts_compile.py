@@ -19,7 +19,8 @@ def test_entry_scripts_and_tools_compile(tmp_path):
 
 
 @pytest.mark.parametrize("script,args", [
-    ("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--mode", "mapping", "--band", "3/8", "--backend", "gloo", "--help"]),
+    ("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--mode", "mapping", "--band", "3/8", "--backend", "gloo", "--full",
+                  "--dump-outputs", "d", "--help"]),
     ("bench_slam.py", ["--frames", "2", "--fused", "--backend", "gloo", "--help"]),
 ])
 def test_argument_parsers_know_the_documented_flags(script, args):

@@ -10,8 +10,8 @@
 # steps:   tests            the whole -m gpu suite, one process
 #          tests:<expr>     pytest -k <expr> of the -m gpu suite (commas for spaces: tests:fused_frame,or,poison)
 #          smoke            __graft_entry__.smoke()
-#          bench            python bench.py (default arguments)
-#          bench:<args>     python bench.py <args>   (commas for spaces: bench:--steps,50,--mode,tracking)
+#          bench            python bench.py --full (default arguments: the whole record)
+#          bench:<args>     python bench.py --full <args>   (commas for spaces: bench:--steps,50,--mode,tracking)
 #          timing           tools/kernel_timing.py at the headline shape (env ABL_* passes through)
 #          timing:<lib>     the same with VTGS_LIBRARY=vtgaussian-slam_amd/lib/<lib>   (A/B builds on the same box)
 #          stamps:<lib>     tools/forward_stamps.py with a -DVTGS_Q_STAMPS build
@@ -64,7 +64,7 @@ for step in "$@"; do
              # (a memory-fault line, a queue error) went into the capture.  Capturing sys.stdout / sys.stderr only lets it through.
              if [ -n "$arg" ]; then run $O/tests_$TAG.log python -m pytest tests/ -x -q -m gpu --capture=sys -k "${arg//,/ }"; else run $O/tests_$TAG.log python -m pytest tests/ -x -q -m gpu --capture=sys; fi ;;
     smoke)   run $O/smoke_$TAG.log python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)   run $O/bench_$TAG.log python bench.py ${arg//,/ } ;;
+    bench)   run $O/bench_$TAG.log python bench.py --full ${arg//,/ } ;;
     timing)  if [ -n "$arg" ]; then VTGS_LIBRARY=$R/vtgaussian-slam_amd/lib/$arg ABL_TAG=$arg run $O/timing_${TAG}_${arg%.so}.log python tools/kernel_timing.py; else ABL_TAG=shipped run $O/timing_$TAG.log python tools/kernel_timing.py; fi ;;
     stamps)  VTGS_LIBRARY=$R/vtgaussian-slam_amd/lib/$arg VTGS_TAIL=40 run $O/stamps_${TAG}.log python tools/forward_stamps.py ;;
     slam)    run $O/slam_$TAG.log python bench_slam.py ${arg//,/ } ;;

@@ -44,7 +44,7 @@ for fused in ("sort_tiles", "finalize_forward"):      # done inside the forward 
     if fused not in f:
         alg["composite_forward"] += alg.pop(fused)
 w = pmc(find("pmc_write", "counter_collection.csv"), "WRITE_SIZE")
-out = {"_note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `bench.py --steps 5 --warmup 2 "
+out = {"_note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `bench.py --full --steps 5 --warmup 2 "
                 "--no-cpu-baseline`; traffic_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch (gfx950 FETCH_SIZE "
                 "correction of MI355X_MICROARCH.md); workload N=1M, 1200x680", "_round": tag,
        # the build the passes ran on (the bench line of the same script run carries it): bench.py quotes these bytes only for
@@ -61,7 +61,7 @@ with open(f"profiles/{tag}_kernel_stats.csv", "w") as fo:
     fo.write(open(find(f"prof_{tag}", "kernel_stats.csv")).read())
 with open(f"profiles/{tag}_kernel_stats.md", "w") as fo:
     fo.write(f"# rocprofv3 --kernel-trace --stats, {tag}\n\ncommand: `rocprofv3 --kernel-trace --stats --output-format csv -- "
-             f"python bench.py --steps 50 --warmup 10 --no-cpu-baseline` (N=1M, 1200x680; the default step counts, so that both runs see the same clocks); bench line of the same build: "
+             f"python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline` (N=1M, 1200x680; the default step counts, so that both runs see the same clocks); bench line of the same build: "
              f"{b['ms_per_step']} ms/step, {b['value']:.4g} {b['unit']}\n\n| kernel | calls | avg us | % |\n|---|---|---|---|\n")
     for r in rows[:12]:
         fo.write(f"| {r['Name'].split('(')[0][:70]} | {r['Calls']} | {float(r['AverageNs'])/1e3:.1f} | {r['Percentage']} |\n")
@@ -87,7 +87,7 @@ except SystemExit:
 if sq:
     occ = {"composite_backward": 3, "composite_forward": 4, "project_and_bin": 8, "gather_splat_grads": 3, "sort_tiles": 6}
     with open(f"profiles/{tag}_sq_counters.md", "w") as fo:
-        fo.write(f"# SQ counters per kernel, {tag} (rocprofv3 --pmc, two passes of `bench.py --steps 3 --warmup 2 "
+        fo.write(f"# SQ counters per kernel, {tag} (rocprofv3 --pmc, two passes of `bench.py --full --steps 3 --warmup 2 "
                  "--no-cpu-baseline`, N=1M, 1200x680)\n\nPercentages are of SQ_WAVE_CYCLES (all SQ_* cycle counters share the "
                  "quad-cycle unit). With w waves resident per SIMD the vector ALU of a SIMD is busy for about "
                  "w x (ACTIVE_INST_VALU %); f32 MFMAs execute on the same fp32 lanes (no co-execution, DESIGN.md 3.2).\n\n"
