@@ -46,6 +46,10 @@ constexpr int kQRing = 64 * kQChunks;       // table / queue ring: 192 slots
 constexpr int kQDummy = kQRing;             // table slot 192: a splat that reaches nothing (popped past the end of a queue)
 constexpr int kSortedIdsInLds = 416;        // sorted ids the wavefront keeps in LDS for its own chunks (4 workgroups per CU: 40 KB each)
 
+// x in [0, 2 kQRing) -> x mod kQRing in two instructions (a subtraction and an unsigned minimum: below kQRing the difference wraps
+// to a huge number) instead of compare + select + subtract
+__device__ __forceinline__ uint32_t q_ring_wrap(uint32_t x) { return min(x, x - (uint32_t)kQRing); }
+
 struct QuadCoord { int tile, px, py, q, i; bool tile_ok, inside; };
 
 __device__ __forceinline__ QuadCoord quad_coord(const CamScalars& cs, uint32_t nblk, int gx16, int gx8, int gy8) {
@@ -220,8 +224,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? 3 : VTGS_Q_WAVES) void composite_f
     int sort_mode, const unsigned long long* __restrict__ bin_keys, const uint32_t* __restrict__ bin_vals,
     uint32_t* sorted_inst, FinalizeArgs fin, uint8_t* __restrict__ qmask, uint32_t* __restrict__ step_counters) {
   constexpr bool DUAL = MODE == 1, ZL = MODE == 2;           // ZL: second image from the depth column
-  // per wavefront: the table of the ring's entries (+ one dummy slot) and the four queues of table slots.  Queue bytes are
-  // stored twice, 128 apart, so a pop reads [head & 127, head & 127 + 16) without wrapping.
+  // per wavefront: the table of the ring's entries (+ one dummy slot) and the four queues of table slots (byte rings of
+  // kQRing positions: q_ring_wrap).
   // The three tables of a wavefront are carved from one block: the counting sort of the tile's list (vtgs_sort_common.h)
   // uses the same bytes as staging before the first chunk is appended.
   constexpr int kTabFloats = (kQRing + 1) * 10 + 2;             // ka 4 + pa 4 + kb 2 floats per slot, 16-byte multiples
@@ -386,19 +390,15 @@ __global__ __launch_bounds__(256, MODE == 1 ? 3 : VTGS_Q_WAVES) void composite_f
     const bool hot = __ballot(in && g1.y > kClampGuard) != 0ull;                                                         \
     const uint32_t mask = in ? quadrant_mask(g0, g1, g0.x - cx, g0.y - cy) : 0u;                                         \
     if (qmask && in) qmask[pos] = (uint8_t)mask;          /* kept for the backward (composite_backward_q) */             \
-    const int tail_v = head_v + c0 + c1 + c2;                                                                            \
+    /* the queue's tail, wrapped ONCE per chunk (head + counts < 2 kQRing); a position then needs one wrap of its own */ \
+    const uint32_t tail_v = q_ring_wrap((uint32_t)(head_v + c0 + c1 + c2));                                              \
     int add_v = 0;                                                                                                       \
     _Pragma("unroll") for (int qq = 0; qq < 4; ++qq) {                                                                   \
       const bool in_q = (mask >> qq) & 1u;                                                                               \
       const unsigned long long bal = __ballot(in_q);                                                                     \
-      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u)); \
-      const int tail = __builtin_amdgcn_readlane(tail_v, 16 * qq);                                                       \
-      if (in_q) {                                                                                                        \
-        int p = tail + rank;                              /* tail < 2 kQRing, rank < 64 */                               \
-        p -= (p >= kQRing) ? kQRing : 0;                                                                                 \
-        p -= (p >= kQRing) ? kQRing : 0;                                                                                 \
-        lds_q[wv][qq][p] = (uint8_t)slot;                                                                                \
-      }                                                                                                                  \
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u)); \
+      const uint32_t tail = (uint32_t)__builtin_amdgcn_readlane((int)tail_v, 16 * qq);                                   \
+      if (in_q) lds_q[wv][qq][q_ring_wrap(tail + rank)] = (uint8_t)slot;        /* tail < kQRing, rank < 64 */           \
       const int add = (int)__builtin_popcountll(bal);                                                                    \
       add_v = (q == qq) ? add : add_v;                                                                                   \
     }                                                                                                                    \
@@ -475,22 +475,23 @@ __global__ __launch_bounds__(256, MODE == 1 ? 3 : VTGS_Q_WAVES) void composite_f
     const unsigned long long ss = __builtin_amdgcn_s_memtime();
 #endif
     const int avail = min(16, c0 + c1 + c2);
-    const int hm = head_v;
+    // Lane i of the group pops entry i of its queue (the dummy past the end); the slots 4 j + (i >> 2) whose payload the lane
+    // feeds to the colour MFMAs are what lanes 4 j + (i >> 2) of the SAME group just popped: four crossbar reads of that
+    // register instead of four more byte reads with their own wrap and dummy select.  The colour MFMAs are the last phase of
+    // the step, so the extra hop is off the path to the first exponent MFMA.  NEEDS ALL 64 LANES ACTIVE (a crossbar read of an
+    // inactive lane returns 0, a real table slot): every exit of this loop is wave-uniform; keep it so.
     int sl[5];
-    auto qwrap = [](int x) { return x >= kQRing ? x - kQRing : x; };
-    sl[4] = (int)myq[qwrap(hm + i)];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sl[j] = (int)myq[qwrap(hm + 4 * j + (i >> 2))];
+    sl[4] = (int)myq[q_ring_wrap((uint32_t)(head_v + i))];
     sl[4] = (i < avail) ? sl[4] : kQDummy;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) sl[j] = (4 * j + (i >> 2) < avail) ? sl[j] : kQDummy;
+    for (int j = 0; j < 4; ++j) sl[j] = __builtin_amdgcn_ds_bpermute(4 * (16 * q + 4 * j + (i >> 2)), sl[4]);
     float PT[4], PT2[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       PT[j] = reinterpret_cast<const float*>(pa)[4 * sl[j] + (i & 3)];
       PT2[j] = DUAL ? reinterpret_cast<const float*>(pb)[4 * sl[j] + (i & 3)] : 0.f;
     }
-    head_v += avail; head_v -= (head_v >= kQRing) ? kQRing : 0;
+    head_v = (int)q_ring_wrap((uint32_t)(head_v + avail));
     {
       int t = avail;
       const int d0 = min(t, c0); c0 -= d0; t -= d0;
