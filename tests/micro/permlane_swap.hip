@@ -1,7 +1,7 @@
 // Self-checking micro-test of the two gfx950 row-swap instructions the backward's quarter reduction relies on:
 //   v_permlane32_swap(a, b): r0 = (a.lanes 0-31 , b.lanes 0-31),  r1 = (a.lanes 32-63, b.lanes 32-63)
 //   v_permlane16_swap(a, b): r0 = (a.row0, b.row0, a.row2, b.row2), r1 = (a.row1, b.row1, a.row3, b.row3)   (rows = 16 lanes)
-// so swap32_add / swap16_add / quarter_sum of vtgs_composite.hip leave row rho holding the 4-row total of register rho.
+// so swap32_add / swap16_add / quarter_sum of vtgs_composite_backward.h leave row rho holding the 4-row total of register rho.
 // Exit code 0 = as assumed.  Build: hipcc --offload-arch=gfx950 permlane_swap.hip -o permlane_swap.bin
 #include <hip/hip_runtime.h>
 #include <stdio.h>

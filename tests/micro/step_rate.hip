@@ -1,13 +1,13 @@
 // step_rate.hip -- how fast can one SIMD run the inner step of the composites when nothing else is in the way?
 //
 // The step functions of vtgs_composite_q.hip (quadrant form: 24 exponent MFMAs + 16 exp/threshold/T updates + 16 colour
-// MFMAs per 16 splats) and of vtgs_composite.hip (lane = pixel form: payload from LDS, colour on the VALU) are run in a
+// MFMAs per 16 splats) and of vtgs_xcheck_composites.hip (lane = pixel form: payload from LDS, colour on the VALU) are run in a
 // loop on register-resident operands, with exactly W wavefronts per SIMD (W blocks of 256 threads per CU, enforced by the
 // dynamic-LDS request).  Prints s_memtime cycles per step for the median wave and the SIMD-level cycles per step
 // (= per-wave cycles / W): the floor the real kernels can approach once memory, LDS queues and control flow are hidden.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../vtgaussian-slam_amd/csrc -I../../include step_rate.hip -o step_rate.bin
 #include "../../vtgaussian-slam_amd/csrc/vtgs_composite_q.hip"
-#include "../../vtgaussian-slam_amd/csrc/vtgs_composite.hip"
+#include "../../vtgaussian-slam_amd/csrc/vtgs_xcheck_composites.hip"
 #include <stdio.h>
 #include <algorithm>
 #include <vector>
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256, 5) void bench_q(unsigned long long* out, int i
   if (l == 0) out[blockIdx.x * 4 + (threadIdx.x >> 6)] = t1 - t0;
 }
 
-// lane = pixel form of vtgs_composite.hip: 24 exponent MFMAs, payload by LDS broadcast reads, colour on the VALU
+// lane = pixel form of vtgs_xcheck_composites.hip: 24 exponent MFMAs, payload by LDS broadcast reads, colour on the VALU
 __global__ __launch_bounds__(256, 3) void bench_px(unsigned long long* out, int iters, float seed, float* sink) {
   extern __shared__ float dyn[];
   __shared__ float4 pay[4][64];

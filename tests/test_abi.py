@@ -182,3 +182,6 @@ def test_cross_check_kernels_live_in_the_test_only_library():
     for kernel in ("composite_forward_mx", "composite_forward_px", "composite_backward_q", "vtgs::composite_forward(", "vtgs::composite_backward("):
         assert kernel not in host, kernel
     assert "composite_forward_q" in host and "composite_backward_mx<4, false, true, false>" in host and "gather_splat_grads" in host
+    # and the other way round: the quad-form backward is the test-only library's, the gradient gather is not
+    xhost = subprocess.run(["nm", "-C", os.path.join(lib_dir, "libvtgs_xcheck.so")], capture_output=True, text=True, check=True).stdout
+    assert "composite_backward_mx<4, false, false, false>" in xhost and "gather_splat_grads" not in xhost

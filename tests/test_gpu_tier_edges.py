@@ -2,7 +2,7 @@
 
 bin_deferred_splats (csrc/vtgs_binning.hip) takes a splat by its candidate-tile area: up to 9 its own lane inside project_and_bin,
 up to 64 a 16-lane group, up to 512 a wavefront, beyond that the workgroup (256 tiles per step, a second pass beyond 131,072).
-gather_splat_grads (csrc/vtgs_composite.hip) takes a splat by its instance count: the lane's own first 4 records, records 5..64
+gather_splat_grads (csrc/vtgs_gather.hip) takes a splat by its instance count: the lane's own first 4 records, records 5..64
 through the wavefront's excess list (windows of 64 positions, owners found by a binary search over the lanes' scan), more than 64
 summed by the whole wavefront.  The random maps of the other tests land somewhere inside these tiers; here every count is chosen.
 

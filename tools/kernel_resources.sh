@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / LDS / scratch use of every kernel in one source file, from the compiler's own remarks (no GPU needed):
-#   tools/kernel_resources.sh vtgaussian-slam_amd/csrc/vtgs_composite.hip [-DFOO ...]
+#   tools/kernel_resources.sh vtgaussian-slam_amd/csrc/vtgs_composite_backward.hip [-DFOO ...]
 f=$1; shift
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$f" -o /dev/null -Rpass-analysis=kernel-resource-usage "$@" 2>&1 |
   awk '/remark: Function Name:/ {name=$(NF-1)}

@@ -10,15 +10,20 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_api.hip", "vtgs_binning.hip", "vtgs_composite.hip", "vtgs_composite_q.hip", "vtgs_frame.hip", "vtgs_loss.hip", "vtgs_p2p.hip", "vtgs_sh.hip")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_api.hip", "vtgs_binning.hip", "vtgs_composite_backward.hip", "vtgs_composite_q.hip",
+                                               "vtgs_frame.hip", "vtgs_gather.hip", "vtgs_loss.hip", "vtgs_p2p.hip", "vtgs_sh.hip")]
 # the cross-check composites (scalar, quad form, lane = pixel forward, quadrant-queue backward): a TEST-ONLY library next to the
-# product, built from the same sources with -DVTGS_XCHECK_BUILD=1; libvtgs.so opens it when an implementation switch asks
-XCHECK_SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_xcheck.hip", "vtgs_composite.hip", "vtgs_composite_bq.hip")]
-HDR = [os.path.join(HERE, "csrc", f) for f in ("vtgs_internal.h", "vtgs_math.h", "vtgs_composite_common.h", "vtgs_sort_common.h")] + \
+# product, from sources of its own (only the header vtgs_composite_backward.h is shared); libvtgs.so opens it when an
+# implementation switch asks
+XCHECK_SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_xcheck.hip", "vtgs_xcheck_composites.hip", "vtgs_composite_bq.hip")]
+HDR = [os.path.join(HERE, "csrc", f) for f in ("vtgs_internal.h", "vtgs_math.h", "vtgs_kernels.h", "vtgs_composite_common.h",
+                                               "vtgs_composite_backward.h", "vtgs_sort_common.h")] + \
       [os.path.join(HERE, "..", "include", "vtgs.h")]
 OUT = os.path.join(HERE, "lib", "libvtgs.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", 
+# --no-undefined: a non-template kernel whose definition drifted from csrc/vtgs_kernels.h is just another overload to the
+# compiler; its launcher's host stub is then missing, and the link says so here instead of the loader on the GPU machine
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wl,--no-undefined",
          "-Wall", "-Wno-unused-function"]
 
 
@@ -39,7 +44,7 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, extra=()) 
         return OUT
     os.makedirs(os.path.dirname(out), exist_ok=True)
     cmd = [HIPCC] + [f for f in FLAGS if f] + list(extra) + SRC + ["-ldl", "-o", out]
-    xcmd = [HIPCC] + [f for f in FLAGS if f] + list(extra) + ["-DVTGS_XCHECK_BUILD=1"] + XCHECK_SRC + ["-o", xcheck_path(out)]
+    xcmd = [HIPCC] + [f for f in FLAGS if f] + list(extra) + XCHECK_SRC + ["-o", xcheck_path(out)]
     if verbose:
         print(" ".join(cmd))
         print(" ".join(xcmd))
@@ -66,8 +71,11 @@ def build_torch_ext(force: bool = False, verbose: bool = False) -> str:
     lib_dir = os.path.dirname(OUT)
     build_dir = os.path.join(lib_dir, "build_vtgs_torch")
     os.makedirs(build_dir, exist_ok=True)
+    # '$$ORIGIN': ninja and then the shell each take one layer off; a bare $ORIGIN reached the linker as an empty entry, and a copy
+    # of the built tree then bound the node to the libvtgs.so of the tree it was built in -- a second instance of the library
+    # next to the one ctypes opens, with its own options and profiler state
     cpp_extension.load(name="vtgs_torch", sources=[TORCH_EXT_SRC], extra_cflags=["-O2", "-std=c++17"],
-                       extra_ldflags=["-L" + lib_dir, "-lvtgs", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + lib_dir],
+                       extra_ldflags=["-L" + lib_dir, "-lvtgs", "-Wl,-rpath,'$$ORIGIN'", "-Wl,-rpath," + lib_dir],
                        build_directory=build_dir, verbose=verbose, is_python_module=False)
     import shutil
     shutil.copy2(os.path.join(build_dir, "vtgs_torch.so"), TORCH_EXT_OUT)

@@ -2,6 +2,7 @@
 // kernel launches on the caller's stream.  No device allocation, no retained pointers.
 #include "../../include/vtgs.h"
 #include "vtgs_internal.h"
+#include "vtgs_kernels.h"
 
 #include <dlfcn.h>
 #include <stdio.h>
@@ -10,40 +11,6 @@
 #include <string>
 
 namespace vtgs {
-// kernels (vtgs_binning.hip / vtgs_composite.hip)
-template <int LDSBINS, int MODE>
-__global__ void project_and_bin(CamScalars, const float*, const float*, int, const float*, const float*, const float*,
-                                const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*,
-                                Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template <int LDSBINS, int MODE>
-__global__ void project_and_bin_capped(CamScalars, const float*, const float*, int, const float*, const float*, const float*,
-                                const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*,
-                                Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template <bool PLANNED>
-__global__ void bin_deferred_splats(CamScalars, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, const DeferRec*,
-                                    uint32_t, unsigned long long, uint32_t, uint32_t);
-__global__ void finalize_forward(const uint32_t*, uint32_t, Counters*, unsigned long long, uint32_t, const BlockStats*,
-                                 uint32_t, VtgsForwardInfo*, const uint32_t*, uint32_t*);
-template <bool WIDE>
-__global__ void sort_tiles(const uint32_t*, unsigned long long*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t,
-                           const Counters*, int, const uint32_t*, uint32_t, unsigned long long, int);
-__global__ void sort_long_lists(const uint32_t*, unsigned long long*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t,
-                                const Counters*, const uint32_t*, uint32_t, unsigned long long, int, uint32_t);
-template <int MODE>
-__global__ void composite_forward_q(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, uint32_t*,
-                                    const GeomRec*, const float*, float*, float*, float*, const Counters*, const float*,
-                                    float*, int, const unsigned long long*, const uint32_t*, uint32_t*, FinalizeArgs, uint8_t*, uint32_t*);
-template <int WAVES, bool DUAL, bool PX, bool B1>
-__global__ void composite_backward_mx(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
-                                      const uint32_t*, const GeomRec*, const float*, const float*, const float*,
-                                      const float*, float*, const Counters*, const float*, const float*, const float*, uint32_t*);
-template <bool DUAL, bool FRAME, bool COV3D, bool B1>
-__global__ void gather_splat_grads(CamScalars, const float*, const float*, int, const float*, const float*, const float*,
-                                   const float*, const GaussAux*, const float*, int, float*, float*, float*, float*, float*,
-                                   float*, const Counters*, float*, FrameEpilogue);
-__global__ void mark_visible_kernel(const float*, int, const float*, uint8_t*);
-__global__ void band_owner_kernel(CamScalars, const float*, const float*, int, const float*, const float*, int, const float*,
-                                  const float*, float, float, const uint8_t*, uint8_t*, uint32_t*, int32_t*);
 __global__ void uniform_plan_kernel(uint32_t* plan, uint32_t entries, uint32_t slots_per_bin) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i < entries) plan[i] = i * slots_per_bin;

@@ -17,6 +17,7 @@
 #include "../../include/vtgs.h"
 #include "vtgs_internal.h"
 #include "vtgs_sort_common.h"
+#include "vtgs_kernels.h"
 
 namespace vtgs {
 
@@ -634,22 +635,22 @@ __global__ __launch_bounds__(kProjBlock) __attribute__((amdgpu_num_sgpr(80))) vo
     DeferRec* __restrict__ defer_list) {
   project_and_bin_body<LDSBINS, MODE>(cs, Vp, PVp, n, means3D, opacities, scales, rotations, radii, geom, gaux, tile_cnt, keys, vals, ctr, block_stats, capacity, tile_cap, defer_list);
 }
-template __global__ void project_and_bin<0, 0>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin<1, 0>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin<2, 0>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<2, 1>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<2, 2>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<2, 3>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<0, 1>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<0, 2>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<0, 3>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<1, 1>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<1, 2>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<1, 3>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<0, 4>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<0, 5>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<1, 4>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
-template __global__ void project_and_bin_capped<1, 5>(CamScalars, const float*, const float*, int, const float*, const float*, const float*, const float*, int32_t*, GeomRec*, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, BlockStats*, unsigned long long, uint32_t, DeferRec*);
+template __global__ decltype(project_and_bin<0, 0>) project_and_bin<0, 0>;
+template __global__ decltype(project_and_bin<1, 0>) project_and_bin<1, 0>;
+template __global__ decltype(project_and_bin<2, 0>) project_and_bin<2, 0>;
+template __global__ decltype(project_and_bin_capped<2, 1>) project_and_bin_capped<2, 1>;
+template __global__ decltype(project_and_bin_capped<2, 2>) project_and_bin_capped<2, 2>;
+template __global__ decltype(project_and_bin_capped<2, 3>) project_and_bin_capped<2, 3>;
+template __global__ decltype(project_and_bin_capped<0, 1>) project_and_bin_capped<0, 1>;
+template __global__ decltype(project_and_bin_capped<0, 2>) project_and_bin_capped<0, 2>;
+template __global__ decltype(project_and_bin_capped<0, 3>) project_and_bin_capped<0, 3>;
+template __global__ decltype(project_and_bin_capped<1, 1>) project_and_bin_capped<1, 1>;
+template __global__ decltype(project_and_bin_capped<1, 2>) project_and_bin_capped<1, 2>;
+template __global__ decltype(project_and_bin_capped<1, 3>) project_and_bin_capped<1, 3>;
+template __global__ decltype(project_and_bin_capped<0, 4>) project_and_bin_capped<0, 4>;
+template __global__ decltype(project_and_bin_capped<0, 5>) project_and_bin_capped<0, 5>;
+template __global__ decltype(project_and_bin_capped<1, 4>) project_and_bin_capped<1, 4>;
+template __global__ decltype(project_and_bin_capped<1, 5>) project_and_bin_capped<1, 5>;
 
 // The deferred splats of a forward (see kDeferArea).  project_and_bin leaves TWO lists in one array: splats of up to kGroupArea
 // candidate tiles from the front (Counters::defer_total), larger ones from the end (Counters::defer_large) -- one list for the
@@ -881,8 +882,8 @@ __global__ __launch_bounds__(kDeferBlock) void bin_deferred_splats(
     // (the next round's first barrier separates this round's readers of s_huge / s_cnt from its writers)
   }
 }
-template __global__ void bin_deferred_splats<false>(CamScalars, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, const DeferRec*, uint32_t, unsigned long long, uint32_t, uint32_t);
-template __global__ void bin_deferred_splats<true>(CamScalars, GaussAux*, uint32_t*, unsigned long long*, uint32_t*, Counters*, const DeferRec*, uint32_t, unsigned long long, uint32_t, uint32_t);
+template __global__ decltype(bin_deferred_splats<false>) bin_deferred_splats<false>;
+template __global__ decltype(bin_deferred_splats<true>) bin_deferred_splats<true>;
 
 // One workgroup right after the binning: longest tile list, statistics, overflow flags and the image of the
 // host-visible VtgsForwardInfo (finalize_block, vtgs_internal.h; the quadrant-queue forward runs it in its first workgroup
@@ -1031,7 +1032,7 @@ __global__ __launch_bounds__(256) void sort_long_lists(const uint32_t* __restric
   for (uint32_t i = t; i < L; i += 256u) { sorted_gid[s + i] = (uint32_t)sk[i]; sorted_inst[s + i] = sv[i]; }
 }
 
-template __global__ void sort_tiles<false>(const uint32_t*, unsigned long long*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, const Counters*, int, const uint32_t*, uint32_t, unsigned long long, int);
-template __global__ void sort_tiles<true>(const uint32_t*, unsigned long long*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, const Counters*, int, const uint32_t*, uint32_t, unsigned long long, int);
+template __global__ decltype(sort_tiles<false>) sort_tiles<false>;
+template __global__ decltype(sort_tiles<true>) sort_tiles<true>;
 
 }  // namespace vtgs

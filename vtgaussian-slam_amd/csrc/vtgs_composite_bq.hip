@@ -1,6 +1,7 @@
-// vtgs_composite_bq.hip -- backward composite with per-quadrant splat queues (gfx950, wave64).
+// vtgs_composite_bq.hip -- backward composite with per-quadrant splat queues (gfx950, wave64).  A cross-check
+// implementation (VTGS_BWD_IMPL=3): compiled into the test-only libvtgs_xcheck.so alone.
 //
-// composite_backward_mx (vtgs_composite.hip) replays every splat of an 8x8 tile's list at all 64 pixels: 0.18 G
+// composite_backward_mx (vtgs_composite_backward.h) replays every splat of an 8x8 tile's list at all 64 pixels: 0.18 G
 // (pixel, splat) pairs at the headline shape, ~85 % of them below alpha = 1/255.  Here, as in composite_forward_q, the 16
 // lanes of a 4x4 QUADRANT walk their own queue of the tile's list -- the entries whose alpha >= 1/255 box reaches the
 // quadrant (the 4-bit masks composite_forward_q left in the workspace; recomputed here when another forward ran) -- so a
@@ -25,14 +26,10 @@
 //     (profiles/r4_lds_accumulate.md): 445 us then, 194 us now.  Fixed order (quadrants 0..3 within a step, steps in
 //     sequence, the step sequence of a tile a function of its list alone): bitwise reproducible run to run.
 //
-// Semantics: SURVEY.md Appendix A4 as restated in vtgs_composite.hip (the recurrences of px_backward_batch).
+// Semantics: SURVEY.md Appendix A4 as restated in vtgs_composite_backward.h (the recurrences of px_backward_batch).
 #include "vtgs_internal.h"
 #include "vtgs_composite_common.h"
-
-#ifndef VTGS_XCHECK_BUILD
-#define VTGS_XCHECK_BUILD 0
-#endif
-#if VTGS_XCHECK_BUILD                          // a cross-check implementation: test-only library (csrc/vtgs_xcheck.hip)
+#include "vtgs_kernels.h"
 
 #ifndef VTGS_BQ_CHUNKS
 #define VTGS_BQ_CHUNKS 2
@@ -81,7 +78,7 @@ struct BqPixel { float T, P, CB; bool done; };   // T frozen once the pixel has 
 __device__ __forceinline__ int img_read_off(int q, int row, int t4) { return q * 256 + row * 16 + 4 * (t4 ^ (row >> 2)); }
 
 // The sweeps of one step for the lane's pixel x the 16 splats its quadrant popped: the recurrences of px_backward_batch
-// (vtgs_composite.hip).  Front to back: alpha_k, w_k = alpha_k T_k -> image row k, T, P.  `wbase[g]` = the lane's image
+// (vtgs_composite_backward.h).  Front to back: alpha_k, w_k = alpha_k T_k -> image row k, T, P.  `wbase[g]` = the lane's image
 // offset for splat group g (rows 4g..4g+3 are 16 floats apart).  Returns with a[], gT[], the anchor in A.
 template <bool CLAMP, bool EXACT_FIRST>
 __device__ __forceinline__ void bq_front(BqPixel& px, bool& exact, const f32x4 (&d)[4], const f32x4 (&gcv)[4], float* __restrict__ img,
@@ -505,5 +502,3 @@ __global__ __launch_bounds__(256, 3) void composite_backward_q(
 }
 
 }  // namespace vtgs
-
-#endif  // VTGS_XCHECK_BUILD

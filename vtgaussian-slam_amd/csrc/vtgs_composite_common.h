@@ -1,5 +1,6 @@
-// vtgs_composite_common.h -- pieces shared by the composite kernels of vtgs_composite.hip (scalar, quad, lane = pixel)
-// and vtgs_composite_q.hip (quadrant queues): tile <-> wavefront mapping, the per-chunk gather, the rank-6 exponent.
+// vtgs_composite_common.h -- pieces shared by the composite kernels: the product's vtgs_composite_q.hip (quadrant-queue
+// forward) and vtgs_composite_backward.h (matrix-core backward), and the cross-checks of vtgs_xcheck_composites.hip /
+// vtgs_composite_bq.hip.  Tile <-> wavefront mapping, the per-chunk gather, the rank-6 exponent.
 #pragma once
 #include "vtgs_internal.h"
 
@@ -117,6 +118,26 @@ __device__ __forceinline__ MxSplat mx_gather(const uint32_t* __restrict__ sorted
 }
 
 constexpr int kExactFirstEndings = 3;   // pixels (of 64) ending in a batch that make the next batch skip the optimistic sweep
+
+// The exponent on the matrix cores.
+// exponent[pixel p, splat k] = log2(alpha_unclamped) = sum_m K_m(k) * Phi_m(p) is bilinear of rank 6:
+//     Phi = (1, X, Y, X^2, XY, Y^2)  with X,Y = pixel - tile centre
+//     K   = (qa sx^2 + qb sx sy + qc sy^2 + log2 o,  -2 qa sx - qb sy,  -2 qc sy - qb sx,  qa, qb, qc),  s = splat centre - tile centre
+// Quad form (mx_exponents): 64 pixels x 16 splats come out of SIX v_mfma_f32_16x16x1_4b_f32 (4 blocks of 16x16, exact f32 fma
+// chains).  With cbsz=2/abid=b the A operand of all four blocks is taken from lanes 16b..16b+15: those lanes' OWN coefficient
+// registers (lane L of the wavefront gathered splat L of the 64-chunk) -- no broadcast instruction at all.
+// B is each lane's own pixel monomials (lane L <-> pixel L of the 8x8 tile), constant for the tile.
+// Result layout (measured, tests/micro/mfma_layout.hip): lane (j = L&15, q = L>>4), register 4*blk + r holds
+//     pixel 16*blk + j,  splat 16*b + 4*q + r.
+// Lane = pixel form (px_exponents): v_mfma_f32_4x4x1_16b_f32 with the A operand broadcast (cbsz = 4, abid = g) gives lane L
+// the exponents of splats 4g..4g+3 at ITS pixel L.
+template <int B>
+__device__ __forceinline__ f32x16 mx_exponents(const float (&K)[6], const float (&Phi)[6]) {
+  f32x16 d = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int m = 0; m < 6; ++m) d = __builtin_amdgcn_mfma_f32_16x16x1f32(K[m], Phi[m], d, 2, B, 0);
+  return d;
+}
 
 template <int G>
 __device__ __forceinline__ f32x4 px_exponents(const float (&K)[6], const float (&Phi)[6]) {

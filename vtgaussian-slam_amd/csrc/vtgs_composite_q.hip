@@ -1,8 +1,9 @@
 // vtgs_composite_q.hip -- composites with per-quadrant splat queues (gfx950, wave64).
 //
-// The lane = pixel kernels of vtgs_composite.hip evaluate every splat of an 8x8 tile's list at all 64 pixels; at view-tied
-// densities (sigma ~ 1 px) a splat's alpha >= 1/255 footprint covers ~2 of the tile's four 4x4 quadrants, so about half of
-// those (pixel, splat) rows are dead by construction.  Here one wavefront is still one 8x8 tile and one lane one pixel, but
+// The lane = pixel kernels (composite_forward_px of vtgs_xcheck_composites.hip, composite_backward_mx of
+// vtgs_composite_backward.h) evaluate every splat of an 8x8 tile's list at all 64 pixels; at view-tied densities
+// (sigma ~ 1 px) a splat's alpha >= 1/255 footprint covers ~2 of the tile's four 4x4 quadrants, so about half of those
+// (pixel, splat) rows are dead by construction.  Here one wavefront is still one 8x8 tile and one lane one pixel, but
 // the 16 lanes of a 4x4 QUADRANT walk their own list:
 //
 //   * lane L <-> pixel (x, y) = (4 (q & 1) + (i & 3), 4 (q >> 1) + (i >> 2)),  q = L >> 4 the quadrant, i = L & 15;
@@ -31,10 +32,11 @@
 // they cost 1.5x the sum of their parts.  The gather is software-pipelined two chunks deep.  With the prefetch registers
 // the kernel needs ~120 VGPRs (4 wavefronts per SIMD); the 64-register form without prefetch runs no faster at 6.
 //
-// Semantics per pixel: SURVEY.md Appendix A3 (see vtgs_composite.hip).
+// Semantics per pixel: SURVEY.md Appendix A3 (see vtgs_composite_backward.h).
 #include "vtgs_internal.h"
 #include "vtgs_composite_common.h"
 #include "vtgs_sort_common.h"
+#include "vtgs_kernels.h"
 
 namespace vtgs {
 
@@ -540,8 +542,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? 3 : VTGS_Q_WAVES) void composite_f
     final_T[pix] = T;
   }
 }
-template __global__ void composite_forward_q<0>(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, uint32_t*, const GeomRec*, const float*, float*, float*, float*, const Counters*, const float*, float*, int, const unsigned long long*, const uint32_t*, uint32_t*, FinalizeArgs, uint8_t*, uint32_t*);
-template __global__ void composite_forward_q<1>(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, uint32_t*, const GeomRec*, const float*, float*, float*, float*, const Counters*, const float*, float*, int, const unsigned long long*, const uint32_t*, uint32_t*, FinalizeArgs, uint8_t*, uint32_t*);
-template __global__ void composite_forward_q<2>(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, uint32_t*, const GeomRec*, const float*, float*, float*, float*, const Counters*, const float*, float*, int, const unsigned long long*, const uint32_t*, uint32_t*, FinalizeArgs, uint8_t*, uint32_t*);
+template __global__ decltype(composite_forward_q<0>) composite_forward_q<0>;
+template __global__ decltype(composite_forward_q<1>) composite_forward_q<1>;
+template __global__ decltype(composite_forward_q<2>) composite_forward_q<2>;
 
 }  // namespace vtgs

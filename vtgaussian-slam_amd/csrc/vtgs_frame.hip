@@ -8,6 +8,7 @@
 // (dL/dt = sum g, dL/dR = sum g p^T; the 12 -> 7 step through the quaternion is done by the caller on 12 floats).
 #include "../../include/vtgs.h"
 #include "vtgs_internal.h"
+#include "vtgs_kernels.h"
 
 namespace vtgs {
 

@@ -2,32 +2,11 @@
 //
 // libvtgs.so ships the default kernels only.  The independent implementations the GPU tests check them against -- the scalar
 // ("readlane") forward and backward, the quad-form matrix-core kernels, the lane = pixel forward, the quadrant-queue backward
-// -- are compiled from the same sources with -DVTGS_XCHECK_BUILD=1 into this library (vtgaussian-slam_amd/build.py), which
+// -- are compiled from vtgs_xcheck_composites.hip and vtgs_composite_bq.hip into this library (vtgaussian-slam_amd/build.py), which
 // libvtgs.so opens next to itself the first time an implementation switch (vtgs_set_option: VTGS_FWD_IMPL / VTGS_BWD_IMPL) asks
 // for one of them.  Without it such a request returns VTGS_ERR_INVALID_ARGUMENT; nothing of the product path is in here.
-#define VTGS_XCHECK_BUILD 1
 #include "vtgs_internal.h"
-
-namespace vtgs {
-__global__ void composite_forward(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
-                                  const GeomRec*, const float*, float*, float*, float*, const Counters*);
-template <int WAVES, bool DUAL>
-__global__ void composite_forward_mx(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
-                                     const GeomRec*, const float*, float*, float*, float*, const Counters*, const float*, float*);
-template <int WAVES, bool DUAL>
-__global__ void composite_forward_px(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
-                                     const GeomRec*, const float*, float*, float*, float*, const Counters*, const float*, float*);
-__global__ void composite_backward(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
-                                   const uint32_t*, const GeomRec*, const float*, const float*, const float*,
-                                   const float*, float*, const Counters*);
-template <int WAVES, bool DUAL, bool PX, bool B1>
-__global__ void composite_backward_mx(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
-                                      const uint32_t*, const GeomRec*, const float*, const float*, const float*,
-                                      const float*, float*, const Counters*, const float*, const float*, const float*, uint32_t*);
-__global__ void composite_backward_q(CamScalars, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
-                                     const uint32_t*, const uint8_t*, const GeomRec*, const float*, const float*, const float*,
-                                     const float*, float*, const Counters*, uint32_t*);
-}  // namespace vtgs
+#include "vtgs_kernels.h"
 
 using namespace vtgs;
 
