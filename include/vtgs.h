@@ -568,6 +568,66 @@ int vtgs_point2plane(int32_t width, int32_t height, const float* depth_target, c
                      const float* w2c_source, float threshold, int32_t frustum, void* scratch, size_t scratch_bytes,
                      float* out_dist, uint8_t* out_matched, void* stream);
 
+/* ---- Exact lower median (the primitive behind depth_error.median(), src/vtgaussian_slam.py:754) ---------------------------
+ * torch.median over a flat float32 tensor, without a host wait: *out_median = the element of rank (n - 1) / 2 in ascending
+ * order; NaN if any value is NaN (*out_nan_count = how many, may be NULL); n = 0 gives NaN and VTGS_OK.  Any float32 is
+ * allowed (negatives, denormals, +-inf); -0 and +0 compare equal, so either may come back when the median is a zero.
+ * Radix select over an order-preserving 32-bit key in three passes (11 + 11 + 10 bits) with integer histograms: exact and
+ * bitwise repeatable.  One fill + three launches + a one-workgroup finish on `stream`; no workgroup waits on another.
+ * n <= 2^32 - 1 (the histograms count in 32 bits); scratch: vtgs_median_scratch_bytes(n) bytes, 16-byte aligned, contents
+ * undefined on entry and exit.                                                                                          */
+size_t vtgs_median_scratch_bytes(int64_t n);
+int vtgs_lower_median(const float* values, int64_t n, void* scratch, size_t scratch_bytes,
+                      float* out_median /*device*/, uint32_t* out_nan_count /*device, may be NULL*/, void* stream);
+
+/* ---- Densification: unexplained pixels -> new Gaussians ------------------------------------------------------
+ * Replaces everything add_new_gaussians_base_frame does after its render (src/vtgaussian_slam.py:748-808, with get_pointcloud
+ * :76-128 and initialize_new_params :692-728), and -- in seed mode -- the point cloud of initialize_params_base_timestep
+ * (:302-340).  The masks restate the reference in float32 with its own operation order (the selected SET is bit-exact):
+ *   err         = |gt_depth - depth_sil[0]| * (gt_depth > 0)                (a literal product: inf * 0 is NaN)
+ *   med         = lower median of err over all H*W pixels
+ *   unexplained = (depth_sil[1] < sil_thres) | ((depth_sil[0] > gt_depth) & (err > 50 * med))
+ *   ori         = unexplained & (gt_depth > 0)
+ *   dense(xd,yd)= (gt_depth_dense > 0) & mask_variation[nearest] & unexplained[nearest]
+ * "nearest" is the source index (xd * src_w) / dst_w in integers (likewise y): cv2.INTER_NEAREST for integer ratios.  The
+ * sizes MUST satisfy dense_width % width == 0, dense_width % mask_width == 0 and the same for the heights (every reference
+ * config is ratio 1 or 2); anything else is VTGS_ERR_INVALID_ARGUMENT.  dense_width == 0: no second set (the dense_* and
+ * mask_* arguments are ignored).  mask_variation == NULL: all set.
+ * Seed mode (depth_sil == NULL): every pixel counts as unexplained, no median is taken (info.median = NaN).
+ * New rows: the ori set in row-major pixel order, then the dense set in row-major pixel order (boolean-mask indexing followed
+ * by torch.cat).  Per row, with (fx, fy, cx, cy) from the image's intrinsics [9] (row-major 3x3, device):
+ *   z' = depth * 1.005;  p_cam = ((x - cx + 0.5) / fx * z', (y - cy + 0.5) / fy * z', z');  means3D = R^T (p_cam - t)
+ *   rgb_colors = the pixel's colour (bit-exact);  unnorm_rotations = (1,0,0,0);  logit_opacities = 0;
+ *   log_scales = log(z' / ((fx + fy) / 2)) in each of scale_columns columns;  timestep = time_idx_value
+ * Pose, exactly one of two forms: w2c [16] row-major (device; must be RIGID: the inverse is taken as R^T, -R^T t), or column t
+ * of the camera tensors cam_unnorm_rots [1,4,frames] / cam_trans [1,3,frames] (R = rotation of the normalised quaternion, as
+ * vtgs_prepare_frame_slot forms it).
+ * The map is caller-owned; rows [n, capacity) are free.  If n + added_ori + added_dense > capacity the call writes NOTHING to
+ * the map and reports overflow = 1 with the two counts (COUNT-ONLY use: capacity = n, or NULL map pointers with capacity = 0;
+ * the caller allocates and calls again).  The map pointers may be NULL only together with capacity = 0; timestep may always
+ * be NULL.  Zero unexplained pixels: added_* = 0, nothing written, VTGS_OK.
+ * One fill + at most five launches on `stream` (seed mode: two launches); no host wait, no device allocation; bitwise
+ * repeatable.  `info` is written by the device (device memory, or pinned device-mapped host memory; `complete` last).
+ * scratch: vtgs_densify_scratch_bytes(...) bytes, 16-byte aligned.  Images: gt_im [3,H,W], gt_depth [H,W], depth_sil [3,H,W]. */
+typedef struct VtgsDensifyInfo {      /* 32 bytes, written by the device */
+  uint32_t added_ori;      /* new Gaussians from the original-resolution image                                          */
+  uint32_t added_dense;    /* ... from the densification-resolution image                                               */
+  uint32_t unexplained;    /* pixels of non_presence_mask (before the valid-depth test): the reference's torch.sum(...) > 0 */
+  uint32_t overflow;       /* 1: n + added_ori + added_dense > capacity; NOTHING was written to the map arrays          */
+  float    median;         /* depth_error.median() (NaN in seed mode or with NaN input)                                 */
+  uint32_t nan_count;
+  uint32_t complete;
+  uint32_t pad;
+} VtgsDensifyInfo;
+size_t vtgs_densify_scratch_bytes(int32_t width, int32_t height, int32_t dense_width, int32_t dense_height);
+int vtgs_densify(int32_t width, int32_t height, const float* depth_sil, const float* gt_im, const float* gt_depth,
+                 const float* intrinsics, int32_t dense_width, int32_t dense_height, const float* gt_im_dense,
+                 const float* gt_depth_dense, const float* intrinsics_dense, const uint8_t* mask_variation, int32_t mask_width,
+                 int32_t mask_height, const float* w2c, const float* cam_unnorm_rots, const float* cam_trans, int32_t frames,
+                 int32_t t, float sil_thres, float time_idx_value, int32_t scale_columns, int32_t n, int32_t capacity,
+                 float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities, float* log_scales,
+                 float* timestep, void* scratch, size_t scratch_bytes, VtgsDensifyInfo* info, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on (used by bench.py for
  * the roofline of the dominant kernel).  While enabled, every kernel launch of the library is bracketed by two
  * events; vtgs_profile_collect synchronises the device, sums elapsed time per kernel name since enabling and

@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <mutex>
 #include <string>
 
@@ -791,6 +792,127 @@ int vtgs_band_owner_mask(const VtgsCamera* cam, int32_t n, const float* means3D,
   hipLaunchKernelGGL(band_owner_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, cs, cam->viewmatrix,
                      cam->projmatrix, n, means3D, scales, scales_are_log ? 1 : 0, cam_q, cam_t, margin_px, growth, owned, mask_out,
                      escapes, centre_rows);
+  VTGS_HIP(hipGetLastError());
+  return VTGS_OK;
+}
+
+// ---- exact lower median and densification (kernels: csrc/vtgs_densify.hip) -------------------------------------------------
+// fill + three histogram passes; the caller launches whatever finishes the select (lower_median_finish, or densify_count)
+static int median_passes(const MedianSource& src, uint32_t n, MedianScratch* ms, hipStream_t st) {
+  {
+    ProfScope ps__("median_clear", st);
+    VTGS_HIP(hipMemsetAsync(ms, 0, kMedianClearBytes, st));
+  }
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + kMedianChunk - 1) / kMedianChunk, kMedianMaxGrid);
+  {
+    ProfScope ps__("lower_median_pass0", st);
+    hipLaunchKernelGGL(lower_median_pass<0>, dim3(grid), dim3(256), 0, st, src, n, ms);
+  }
+  {
+    ProfScope ps__("lower_median_pass1", st);
+    hipLaunchKernelGGL(lower_median_pass<1>, dim3(grid), dim3(256), 0, st, src, n, ms);
+  }
+  {
+    ProfScope ps__("lower_median_pass2", st);
+    hipLaunchKernelGGL(lower_median_pass<2>, dim3(grid), dim3(256), 0, st, src, n, ms);
+  }
+  VTGS_HIP(hipGetLastError());
+  return VTGS_OK;
+}
+
+size_t vtgs_median_scratch_bytes(int64_t n) {
+  if (n < 0 || n > 0xFFFFFFFFll) return 0;
+  return align256(sizeof(MedianScratch));
+}
+
+int vtgs_lower_median(const float* values, int64_t n, void* scratch, size_t scratch_bytes, float* out_median,
+                      uint32_t* out_nan_count, void* stream) {
+  if (n < 0 || n > 0xFFFFFFFFll || (n > 0 && !values) || !scratch || ((uintptr_t)scratch & 15u) || !out_median)
+    return VTGS_ERR_INVALID_ARGUMENT;
+  if (scratch_bytes < vtgs_median_scratch_bytes(n)) return VTGS_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t st = (hipStream_t)stream;
+  MedianScratch* ms = (MedianScratch*)scratch;
+  if (n > 0) {
+    const MedianSource src{values, nullptr, nullptr};
+    const int rc = median_passes(src, (uint32_t)n, ms, st);
+    if (rc != VTGS_OK) return rc;
+  }
+  ProfScope ps__("lower_median_finish", st);
+  hipLaunchKernelGGL(lower_median_finish, dim3(1), dim3(256), 0, st, (uint32_t)n, ms, out_median, out_nan_count);
+  VTGS_HIP(hipGetLastError());
+  return VTGS_OK;
+}
+
+static bool densify_sizes_ok(int32_t w, int32_t h, int32_t dw, int32_t dh) {
+  if (w <= 0 || h <= 0 || (int64_t)w * h > 0x7FFFFFFFll - kDensifyChunk) return false;
+  if (dw == 0) return true;
+  return dw > 0 && dh > 0 && (int64_t)dw * dh <= 0x7FFFFFFFll - kDensifyChunk && dw % w == 0 && dh % h == 0;
+}
+static uint32_t densify_chunks(int32_t w, int32_t h) { return (uint32_t)(((int64_t)w * h + kDensifyChunk - 1) / kDensifyChunk); }
+
+size_t vtgs_densify_scratch_bytes(int32_t width, int32_t height, int32_t dense_width, int32_t dense_height) {
+  if (!densify_sizes_ok(width, height, dense_width, dense_height)) return 0;
+  const size_t bo = densify_chunks(width, height), bd = dense_width ? densify_chunks(dense_width, dense_height) : 0;
+  return align256(sizeof(MedianScratch)) + align256((bo + bd) * 4) + align256(bo * 4);
+}
+
+int vtgs_densify(int32_t width, int32_t height, const float* depth_sil, const float* gt_im, const float* gt_depth,
+                 const float* intrinsics, int32_t dense_width, int32_t dense_height, const float* gt_im_dense,
+                 const float* gt_depth_dense, const float* intrinsics_dense, const uint8_t* mask_variation, int32_t mask_width,
+                 int32_t mask_height, const float* w2c, const float* cam_unnorm_rots, const float* cam_trans, int32_t frames,
+                 int32_t t, float sil_thres, float time_idx_value, int32_t scale_columns, int32_t n, int32_t capacity,
+                 float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities, float* log_scales,
+                 float* timestep, void* scratch, size_t scratch_bytes, VtgsDensifyInfo* info, void* stream) {
+  if (!densify_sizes_ok(width, height, dense_width, dense_height) || !gt_im || !gt_depth || !intrinsics || !scratch ||
+      ((uintptr_t)scratch & 15u) || !info || n < 0 || capacity < 0 || (scale_columns != 1 && scale_columns != 3))
+    return VTGS_ERR_INVALID_ARGUMENT;
+  const bool quat = cam_unnorm_rots || cam_trans;
+  if ((w2c != nullptr) == quat) return VTGS_ERR_INVALID_ARGUMENT;                    // exactly one pose form
+  if (quat && (!cam_unnorm_rots || !cam_trans || frames <= 0 || t < 0 || t >= frames)) return VTGS_ERR_INVALID_ARGUMENT;
+  if (capacity > 0 && (!means3D || !rgb_colors || !unnorm_rotations || !logit_opacities || !log_scales))
+    return VTGS_ERR_INVALID_ARGUMENT;
+  DensifyArgs a{};
+  a.W = width; a.H = height; a.dW = dense_width; a.dH = dense_width ? dense_height : 0;
+  a.rx = a.ry = a.mrx = a.mry = 1; a.mW = 0;
+  if (dense_width) {
+    if (!gt_im_dense || !gt_depth_dense || !intrinsics_dense) return VTGS_ERR_INVALID_ARGUMENT;
+    a.rx = dense_width / width; a.ry = dense_height / height;
+    if (mask_variation) {
+      if (mask_width <= 0 || mask_height <= 0 || dense_width % mask_width || dense_height % mask_height)
+        return VTGS_ERR_INVALID_ARGUMENT;
+      a.mrx = dense_width / mask_width; a.mry = dense_height / mask_height; a.mW = mask_width;
+      a.mask = mask_variation;
+    }
+    a.gt_im_d = gt_im_dense; a.gt_depth_d = gt_depth_dense; a.k_d = intrinsics_dense;
+  }
+  if (scratch_bytes < vtgs_densify_scratch_bytes(width, height, dense_width, dense_height)) return VTGS_ERR_WORKSPACE_TOO_SMALL;
+  a.depth_sil = depth_sil; a.gt_im = gt_im; a.gt_depth = gt_depth; a.k = intrinsics;
+  a.w2c = w2c; a.cam_rots = cam_unnorm_rots; a.cam_trans = cam_trans; a.frames = frames; a.t = t;
+  a.sil_thres = sil_thres; a.time_value = time_idx_value; a.scale_columns = scale_columns; a.n = n; a.capacity = capacity;
+  a.means3D = means3D; a.rgb = rgb_colors; a.rot = unnorm_rotations; a.opac = logit_opacities; a.log_scales = log_scales;
+  a.timestep = timestep;
+  a.blocks_ori = densify_chunks(width, height);
+  a.blocks_dense = dense_width ? densify_chunks(dense_width, dense_height) : 0u;
+  char* base = (char*)scratch;
+  a.ms = (MedianScratch*)base;
+  a.counts = (uint32_t*)(base + align256(sizeof(MedianScratch)));
+  a.unexplained = (uint32_t*)(base + align256(sizeof(MedianScratch)) + align256(((size_t)a.blocks_ori + a.blocks_dense) * 4));
+  a.info = info;
+  hipStream_t st = (hipStream_t)stream;
+  if (depth_sil) {                                  // the median of the depth error, formed on the fly by the three passes
+    const MedianSource src{nullptr, depth_sil, gt_depth};
+    const int rc = median_passes(src, (uint32_t)(width * height), a.ms, st);
+    if (rc != VTGS_OK) return rc;
+  }
+  const uint32_t grid = a.blocks_ori + a.blocks_dense;
+  {
+    ProfScope ps__("densify_count", st);
+    hipLaunchKernelGGL(densify_count, dim3(grid), dim3(256), 0, st, a);
+  }
+  {
+    ProfScope ps__("densify_emit", st);
+    hipLaunchKernelGGL(densify_emit, dim3(grid), dim3(256), 0, st, a);
+  }
   VTGS_HIP(hipGetLastError());
   return VTGS_OK;
 }

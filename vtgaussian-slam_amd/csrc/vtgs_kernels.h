@@ -91,6 +91,51 @@ __global__ void band_owner_kernel(
     float margin_px, float growth, const uint8_t* __restrict__ owned, uint8_t* __restrict__ mask_out,
     uint32_t* __restrict__ escapes, int32_t* __restrict__ centre_rows);
 
+// ---- vtgs_densify.hip: exact lower median (radix select) and the densification step ------------------------------------------
+constexpr uint32_t kMedianChunk = 4096;     // values a workgroup of 256 takes per trip (16 per thread); grid-stride beyond kMedianMaxGrid
+constexpr uint32_t kMedianMaxGrid = 1024;
+// Head of the caller's scratch.  The three histograms and the NaN counter are zeroed by ONE fill in front of pass 0; the words
+// behind them are written by workgroup 0 of a pass for the workgroups of the next (every field is written before it is read).
+struct alignas(16) MedianScratch {
+  uint32_t hist0[2048], hist1[2048], hist2[1024];   // key bits 31..21, 20..10, 9..0
+  uint32_t nan_count, pad0[3];
+  uint32_t digit0, rank1;        // pass 1: the bucket of hist0 that holds the rank, and the rank inside it
+  uint32_t prefix2, rank2;       // pass 2: key bits 31..10 of the median, and the rank among the keys that share them
+  float median;                  // densify_count: the value, for densify_emit
+  uint32_t pad1[3];
+};
+constexpr size_t kMedianClearBytes = offsetof(MedianScratch, digit0);
+static_assert(sizeof(MedianScratch) % 16 == 0 && offsetof(MedianScratch, hist1) % 16 == 0 && offsetof(MedianScratch, hist2) % 16 == 0,
+              "MedianScratch: the bucket search reads the histograms as 16-byte words");
+// what the median is taken of: `values`, or (values == NULL) the depth error |gt_depth - depth| * (gt_depth > 0) formed on the fly
+struct MedianSource { const float* values; const float* depth; const float* gt_depth; };
+template <int PASS>
+__global__ void lower_median_pass(MedianSource src, uint32_t n, MedianScratch* __restrict__ ms);
+__global__ void lower_median_finish(uint32_t n, MedianScratch* __restrict__ ms, float* __restrict__ out_median,
+                                    uint32_t* __restrict__ out_nan_count);
+
+constexpr uint32_t kDensifyChunk = 512;     // consecutive pixels per workgroup of 256 (two steps): one count per chunk
+struct DensifyArgs {
+  int W, H, dW, dH;                         // dW == 0: no dense set
+  int rx, ry, mrx, mry;                     // dW / W, dH / H; dW / mask width, dH / mask height (the integer nearest rule)
+  int mW;
+  const float* depth_sil;                   // [3,H,W]; NULL = seed mode
+  const float* gt_im; const float* gt_depth; const float* k;
+  const float* gt_im_d; const float* gt_depth_d; const float* k_d;
+  const uint8_t* mask;                      // NULL = all set
+  const float* w2c; const float* cam_rots; const float* cam_trans; int frames, t;
+  float sil_thres, time_value;
+  int scale_columns, n, capacity;
+  float* means3D; float* rgb; float* rot; float* opac; float* log_scales; float* timestep;
+  MedianScratch* ms;
+  uint32_t* counts;                         // [blocks_ori + blocks_dense] selected pixels per chunk, ori chunks first
+  uint32_t* unexplained;                    // [blocks_ori] pixels of the non-presence mask per chunk
+  uint32_t blocks_ori, blocks_dense;
+  VtgsDensifyInfo* info;
+};
+__global__ void densify_count(DensifyArgs a);
+__global__ void densify_emit(DensifyArgs a);
+
 // ---- the cross-check composites of the test-only libvtgs_xcheck.so (vtgs_xcheck_composites.hip, vtgs_composite_bq.hip) -------
 __global__ void composite_forward(
     CamScalars cs, const float* __restrict__ bg, uint32_t nblk,
