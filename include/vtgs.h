@@ -628,6 +628,44 @@ int vtgs_densify(int32_t width, int32_t height, const float* depth_sil, const fl
                  float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities, float* log_scales,
                  float* timestep, void* scratch, size_t scratch_bytes, VtgsDensifyInfo* info, void* stream);
 
+/* ---- Keyframe overlap selection: all keyframes in one device pass ------------------------------------------
+ * The counting behind keyframe_selection_overlap, ..._visbased, ..._visbased_earliest_dynamic_new_topkbase and
+ * find_earliest_keyframe (utils/keyframe_selection.py:40-116, 121-229, 581-724, 1581-1613): the points of the current frame
+ * are back-projected once and tested against every selected keyframe; the host reads k + 3 integers.  float32 throughout:
+ *   source (row r, col c), z = depth[r, c]:   p_cam = ((c - cx) / fx * z, (r - cy) / fy * z, z),  p = c2w p_cam
+ *     (fx, fy, cx, cy = intrinsics[0], [4], [2], [5]; c2w = the rigid inverse R^T (p_cam - t) of w2c)
+ *   origin rule: the point is DROPPED when rintf(p_i * 1e4f) == 0 for all three components (the reference's "remove points
+ *     at camera origin": round(decimals = 4), abs, equal to the zero row)
+ *   keyframe j (row s = slots[j], or j):  q = (K [R|t]_s) p,  z' = q.z + 1e-5,  u = q.x / z',  v = q.y / z'
+ *     (K = the full 3x3 `intrinsics`; K [R|t] is folded once per call)
+ *     in  = (u < W - edge) & (u > edge) & (v < H - edge) & (v > edge) & (z' > 0)
+ *     kf_depth given:  d = bilinear sample of kf_depth[s] at (u, v) in pixel units (grid_sample, align_corners = True, zero
+ *       padding: a tap at column W or row H, reachable only with edge < 1, contributes 0);
+ *       vis = |d - z'| < kf_depth_thresh * min(d, z');   counts[j] += in & vis.      kf_depth == NULL: counts[j] += in.
+ * Sources.  Dense (sampled_rc == NULL, samples == 0): every pixel with depth > 0.  Sampled: `samples` (row, col) int32 pairs,
+ *   1 <= samples <= 16384.  Repeat rule: a sample whose pixel occurs MORE THAN ONCE in the list is dropped in ALL its copies
+ *   (the reference draws with replacement and its unique(..., return_counts = True) removes every copy of a repeated row).
+ *   A sample outside the image or on a pixel with depth <= 0 is no source at all (the reference never draws one).
+ *   NOT reproduced: the reference also drops two DIFFERENT pixels whose |rounded| world coordinates coincide -- an accident of
+ *   the same unique() call.
+ * record (device, 4-byte aligned, k + 3 words, zeroed by the library on `stream`):
+ *   [0, k) counts   [k] kept points n (the reference's denominator)   [k + 1] valid-depth sources   [k + 2] dropped
+ *   (repeats + origin points: [k + 1] - [k]).  n == 0: every count is 0; nothing divides.
+ * pair_mask (NULL in production): [k][S] bytes, S = H * W (dense, indexed by pixel) or `samples`: in & vis per pair; 0xFF for
+ *   a pixel / sample that is no source or was dropped.
+ * kf_w2c [cap][16] / kf_depth [cap][H * W]: resident tables; `slots` (device int32 [k], may repeat, NULL = 0 .. k - 1) selects
+ *   rows.  Rows must lie inside the tables (the library cannot know cap); a negative slot counts 0.
+ * Refused with VTGS_ERR_INVALID_ARGUMENT before any device work: non-positive or oversized sizes, k <= 0 or > 2^20, samples
+ *   outside the rule above, a NULL depth / intrinsics / w2c / kf_w2c / record / scratch, a record that is not 4-byte aligned,
+ *   a scratch that is not 16-byte aligned or smaller than vtgs_keyframe_overlap_scratch_bytes(...) (0 for invalid sizes), an
+ *   edge that is negative or not finite.  One or two fills + two or three launches on `stream`; no host wait, no device
+ *   allocation; integer adds: order-independent and bitwise repeatable.                                                    */
+size_t vtgs_keyframe_overlap_scratch_bytes(int32_t width, int32_t height, int32_t samples, int32_t k);
+int vtgs_keyframe_overlap(int32_t width, int32_t height, const float* depth, const float* intrinsics, const float* w2c,
+                          const int32_t* sampled_rc, int32_t samples, const float* kf_w2c, const float* kf_depth,
+                          const int32_t* slots, int32_t k, float edge, float kf_depth_thresh, uint8_t* pair_mask,
+                          void* scratch, size_t scratch_bytes, uint32_t* record, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on (used by bench.py for
  * the roofline of the dominant kernel).  While enabled, every kernel launch of the library is bracketed by two
  * events; vtgs_profile_collect synchronises the device, sums elapsed time per kernel name since enabling and

@@ -917,6 +917,66 @@ int vtgs_densify(int32_t width, int32_t height, const float* depth_sil, const fl
   return VTGS_OK;
 }
 
+// ---- keyframe overlap counts (kernels: csrc/vtgs_keyframes.hip) ----------------------------------------------------------------
+static bool keyframe_sizes_ok(int32_t w, int32_t h, int32_t samples, int32_t k) {
+  return w > 0 && h > 0 && (int64_t)w * h <= 0x7FFFFFFFll - 256 && samples >= 0 && samples <= 16384 && k > 0 && k <= (1 << 20);
+}
+static size_t keyframe_bitmap_bytes(int32_t w, int32_t h) { return align256((((size_t)w * h + 31) / 32) * 4); }
+
+size_t vtgs_keyframe_overlap_scratch_bytes(int32_t width, int32_t height, int32_t samples, int32_t k) {
+  if (!keyframe_sizes_ok(width, height, samples, k)) return 0;
+  return align256((size_t)k * sizeof(KeyframeRow)) + (samples ? 2 * keyframe_bitmap_bytes(width, height) : 0);
+}
+
+int vtgs_keyframe_overlap(int32_t width, int32_t height, const float* depth, const float* intrinsics, const float* w2c,
+                          const int32_t* sampled_rc, int32_t samples, const float* kf_w2c, const float* kf_depth,
+                          const int32_t* slots, int32_t k, float edge, float kf_depth_thresh, uint8_t* pair_mask,
+                          void* scratch, size_t scratch_bytes, uint32_t* record, void* stream) {
+  if (!keyframe_sizes_ok(width, height, samples, k) || !depth || !intrinsics || !w2c || !kf_w2c || !record ||
+      ((uintptr_t)record & 3u) || !scratch || ((uintptr_t)scratch & 15u) || (sampled_rc != nullptr) != (samples > 0) ||
+      ((uintptr_t)sampled_rc & 3u) || !(edge >= 0.f) || !(edge <= 3.0e38f))
+    return VTGS_ERR_INVALID_ARGUMENT;
+  if (scratch_bytes < vtgs_keyframe_overlap_scratch_bytes(width, height, samples, k)) return VTGS_ERR_INVALID_ARGUMENT;
+  KeyframeArgs a{};
+  a.W = width; a.H = height; a.depth = depth; a.k = intrinsics; a.w2c = w2c; a.sampled_rc = sampled_rc; a.samples = samples;
+  a.kf_w2c = kf_w2c; a.kf_depth = kf_depth; a.slots = slots; a.K = k; a.edge = edge; a.thresh = kf_depth_thresh;
+  a.pair_mask = pair_mask; a.record = record;
+  char* base = (char*)scratch;
+  a.rows = (KeyframeRow*)base;
+  const size_t bm = keyframe_bitmap_bytes(width, height);
+  if (samples) {
+    a.seen = (uint32_t*)(base + align256((size_t)k * sizeof(KeyframeRow)));
+    a.repeated = (uint32_t*)((char*)a.seen + bm);
+  }
+  const uint32_t sources = samples ? (uint32_t)samples : (uint32_t)(width * height);
+  const uint32_t gx = (sources + 255u) / 256u;
+  // keyframes over blockIdx.y until the grid holds about four workgroups per CU; a slice never exceeds the LDS counters
+  uint32_t slices = std::min<uint32_t>((uint32_t)k, std::max<uint32_t>(1u, (1024u + gx - 1u) / gx));
+  slices = std::max<uint32_t>(slices, ((uint32_t)k + kKeyframeSliceMax - 1u) / kKeyframeSliceMax);
+  a.per_slice = ((uint32_t)k + slices - 1u) / slices;
+  slices = ((uint32_t)k + a.per_slice - 1u) / a.per_slice;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope ps__("keyframe_clear", st);
+    VTGS_HIP(hipMemsetAsync(record, 0, ((size_t)k + 3) * 4, st));
+    if (samples) VTGS_HIP(hipMemsetAsync(a.seen, 0, 2 * bm, st));
+  }
+  {
+    ProfScope ps__("keyframe_fold", st);
+    hipLaunchKernelGGL(keyframe_fold, dim3(std::min<uint32_t>(((uint32_t)k + 255u) / 256u, 64u)), dim3(256), 0, st, a);
+  }
+  if (samples) {
+    ProfScope ps__("keyframe_mark_repeats", st);
+    hipLaunchKernelGGL(keyframe_mark_repeats, dim3(gx), dim3(256), 0, st, a);
+  }
+  {
+    ProfScope ps__("keyframe_overlap", st);
+    hipLaunchKernelGGL(keyframe_overlap, dim3(gx, slices), dim3(256), 0, st, a, (const KeyframeRow*)a.rows);
+  }
+  VTGS_HIP(hipGetLastError());
+  return VTGS_OK;
+}
+
 int vtgs_profile_enable(int on) {
   g_prof_on = on != 0;
   g_prof_n = 0;

@@ -136,6 +136,30 @@ struct DensifyArgs {
 __global__ void densify_count(DensifyArgs a);
 __global__ void densify_emit(DensifyArgs a);
 
+// ---- vtgs_keyframes.hip: keyframe overlap counts, all keyframes in one pass ----------------------------------------------------
+constexpr uint32_t kKeyframeSliceMax = 256;   // keyframes per blockIdx.y slice at most: the LDS counters of a workgroup
+struct alignas(16) KeyframeRow {              // written by keyframe_fold for keyframe_overlap (uniform loads)
+  float m[12];                                // K [R|t] of the keyframe, row-major 3x4
+  int32_t slot;                               // row of kf_depth (negative: the keyframe counts 0)
+  uint32_t pad[3];
+};
+struct KeyframeArgs {
+  int W, H;
+  const float* depth; const float* k; const float* w2c;
+  const int32_t* sampled_rc; int samples;     // NULL, 0: dense
+  const float* kf_w2c; const float* kf_depth; const int32_t* slots; int K;
+  float edge, thresh;
+  uint8_t* pair_mask;
+  KeyframeRow* rows;                          // [K]
+  uint32_t* seen; uint32_t* repeated;         // sampled mode: a bit per pixel each, zeroed in front of keyframe_mark_repeats
+  uint32_t* record;                           // [K + 3]
+  uint32_t per_slice;                         // keyframes per blockIdx.y
+};
+__global__ void keyframe_fold(KeyframeArgs a);
+__global__ void keyframe_mark_repeats(KeyframeArgs a);
+// `rows` = a.rows as a read-only, non-aliased kernel argument: the loop's row loads become scalar loads
+__global__ void keyframe_overlap(KeyframeArgs a, const KeyframeRow* __restrict__ rows);
+
 // ---- the cross-check composites of the test-only libvtgs_xcheck.so (vtgs_xcheck_composites.hip, vtgs_composite_bq.hip) -------
 __global__ void composite_forward(
     CamScalars cs, const float* __restrict__ bg, uint32_t nblk,
