@@ -666,6 +666,45 @@ int vtgs_keyframe_overlap(int32_t width, int32_t height, const float* depth, con
                           const int32_t* slots, int32_t k, float edge, float kf_depth_thresh, uint8_t* pair_mask,
                           void* scratch, size_t scratch_bytes, uint32_t* record, void* stream);
 
+/* ---- Tracking masks: visibility, outlier depth and far depth in one pass ----------------------------------------------------
+ * The detached masks get_loss forms on every tracking iteration for TUM, ScanNet and ScanNet++ (src/vtgaussian_slam.py:
+ * 525-528 outlier depth, 536-584 with get_vis_mask 376-404 visibility, 586-588 far depth), ANDed, as the [H*W] float 0 / 1
+ * `extra_mask` of vtgs_slam_loss* above.  float32 throughout; every pose is read on the device:
+ *   pixel p = (row r, col c), z = gt_depth[p]:  p_cam = ((c - cx) / fx * z, (r - cy) / fy * z, z)
+ *     (fx, fy, cx, cy = intrinsics[0], [4], [2], [5])
+ *   overlap j < n_overlaps:  q = M_j [p_cam; 1],  M_j = K W_j[:3,:] inverse(curr_w2c)  (3x4, folded once per call in double,
+ *     rounded once; K = the full 3x3 `intrinsics`),  z' = q.z + 1e-5,  u = q.x / z',  v = q.y / z'
+ *     d = bilinear sample of overlap_depth[j] at (u, v) in pixel units (grid_sample, align_corners = True, zero padding):
+ *       each of the four taps is tested against the image on its own, so u in (-1, 0) or (W - 1, W) still takes one in-image
+ *       column; a point wholly outside, or a u / v that is not finite, samples 0.  No edge test, no z' > 0 test (the
+ *       reference has neither; with non-negative depth maps the comparison below is false for z' <= 0 on its own)
+ *     vis_j = |d - z'| < vis_thres * min(d, z');   visibility = OR over j.   n_overlaps == 0: no visibility mask.
+ *   use_far:  & (gt_depth[p] < far_thres)
+ *   rendered_depth (plane 0 of the depth / silhouette render) given:  err[p] = |gt_depth[p] - rendered_depth[p]| *
+ *     (gt_depth[p] > 0), median = the element of rank (H*W - 1) / 2 of err (torch.median; the radix select of
+ *     vtgs_lower_median, exact, kept in device memory);  & (err[p] < 50 * median) & (gt_depth[p] > 0).  A NaN in err makes the
+ *     median NaN and every pixel 0, as in torch.
+ *   out_mask[p] = 1.0f / 0.0f;  out_mask_u8 (may be NULL): the same as bytes;  out_vis_bits (may be NULL): vis_j in bit j.
+ *   Nothing requested (no overlaps, no far filter, no rendered depth): out_mask is filled with ones.
+ * Two deviations from the reference.  inverse(curr_w2c) is the rigid inverse [R^T | -R^T t], not torch.inverse's LU (equal
+ *   for a rigid pose up to rounding).  A pixel with gt_depth < 0 or NaN has visibility 0: the reference drops it from its
+ *   point list (gt_depth >= 0) and then fails at the reshape to [H, W], so no valid input takes this path.
+ * overlap_w2c / overlap_depth: HOST arrays of n_overlaps device pointers ([16] floats, [H*W] floats), read during the call.
+ * Refused with VTGS_ERR_INVALID_ARGUMENT before any device work: non-positive or oversized sizes, n_overlaps outside 0..3,
+ *   a NULL gt_depth / out_mask, with n_overlaps > 0 a NULL intrinsics / curr_w2c / array / array entry, a scratch that is
+ *   needed (vtgs_tracking_mask_scratch_bytes(...) > 0; outlier = rendered_depth != NULL) and is NULL, not 16-byte aligned or
+ *   smaller than that.  vtgs_tracking_mask_scratch_bytes is 0 for invalid sizes.
+ * Launches on `stream`: 1 (mask) + 1 (fold, n_overlaps > 0) + 1 fill + 5 (error, three select passes, finish; outlier mask).
+ *   No host wait, no device allocation, no atomics outside the select's integer histograms: bitwise repeatable.          */
+size_t vtgs_tracking_mask_scratch_bytes(int32_t width, int32_t height, int32_t n_overlaps, int32_t outlier);
+int vtgs_tracking_mask(int32_t width, int32_t height, const float* gt_depth, const float* intrinsics /*dev [9]*/,
+                       const float* curr_w2c /*dev [16], NULL iff n_overlaps == 0*/,
+                       int32_t n_overlaps /*0..3*/, const float* const* overlap_w2c /*host array of dev [16]*/,
+                       const float* const* overlap_depth /*host array of dev [H*W]*/, float vis_thres,
+                       int32_t use_far, float far_thres, const float* rendered_depth /*dev [H*W], NULL = no outlier mask*/,
+                       void* scratch, size_t scratch_bytes, float* out_mask, uint8_t* out_mask_u8 /*may be NULL*/,
+                       uint8_t* out_vis_bits /*may be NULL*/, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on (used by bench.py for
  * the roofline of the dominant kernel).  While enabled, every kernel launch of the library is bracketed by two
  * events; vtgs_profile_collect synchronises the device, sums elapsed time per kernel name since enabling and

@@ -977,6 +977,71 @@ int vtgs_keyframe_overlap(int32_t width, int32_t height, const float* depth, con
   return VTGS_OK;
 }
 
+// ---- tracking masks: visibility, far depth, outlier depth (kernels: csrc/vtgs_masks.hip) -----------------------------------------
+static bool mask_sizes_ok(int32_t w, int32_t h, int32_t n, int32_t outlier) {
+  return w > 0 && h > 0 && (int64_t)w * h <= 0x7FFFFFFFll - 256 && n >= 0 && n <= 3 && (outlier == 0 || outlier == 1);
+}
+// scratch: [folded rows] [MedianScratch] [the median, one float] [err, H*W floats]; the last three only with the outlier mask
+static size_t mask_rows_bytes(int32_t n) { return align256((size_t)n * sizeof(MaskRow)); }
+
+size_t vtgs_tracking_mask_scratch_bytes(int32_t width, int32_t height, int32_t n_overlaps, int32_t outlier) {
+  if (!mask_sizes_ok(width, height, n_overlaps, outlier)) return 0;
+  size_t b = mask_rows_bytes(n_overlaps);
+  if (outlier) b += align256(sizeof(MedianScratch)) + 256 + align256((size_t)width * height * 4);
+  return b;
+}
+
+int vtgs_tracking_mask(int32_t width, int32_t height, const float* gt_depth, const float* intrinsics, const float* curr_w2c,
+                       int32_t n_overlaps, const float* const* overlap_w2c, const float* const* overlap_depth, float vis_thres,
+                       int32_t use_far, float far_thres, const float* rendered_depth, void* scratch, size_t scratch_bytes,
+                       float* out_mask, uint8_t* out_mask_u8, uint8_t* out_vis_bits, void* stream) {
+  const int32_t outlier = rendered_depth ? 1 : 0;
+  if (!mask_sizes_ok(width, height, n_overlaps, outlier) || !gt_depth || !out_mask) return VTGS_ERR_INVALID_ARGUMENT;
+  if (n_overlaps > 0) {
+    if (!intrinsics || !curr_w2c || !overlap_w2c || !overlap_depth) return VTGS_ERR_INVALID_ARGUMENT;
+    for (int32_t j = 0; j < n_overlaps; ++j)
+      if (!overlap_w2c[j] || !overlap_depth[j]) return VTGS_ERR_INVALID_ARGUMENT;
+  }
+  const size_t need = vtgs_tracking_mask_scratch_bytes(width, height, n_overlaps, outlier);
+  if (need && (!scratch || ((uintptr_t)scratch & 15u) || scratch_bytes < need)) return VTGS_ERR_INVALID_ARGUMENT;
+  MaskArgs a{};
+  a.W = width; a.H = height; a.n = n_overlaps; a.gt = gt_depth; a.k = intrinsics; a.curr_w2c = curr_w2c;
+  if (n_overlaps > 0) { a.ov_w2c0 = overlap_w2c[0]; a.ov_depth0 = overlap_depth[0]; }
+  if (n_overlaps > 1) { a.ov_w2c1 = overlap_w2c[1]; a.ov_depth1 = overlap_depth[1]; }
+  if (n_overlaps > 2) { a.ov_w2c2 = overlap_w2c[2]; a.ov_depth2 = overlap_depth[2]; }
+  a.thres = vis_thres; a.use_far = use_far ? 1 : 0; a.far = far_thres; a.rendered = rendered_depth;
+  a.out = out_mask; a.out_u8 = out_mask_u8; a.out_bits = out_vis_bits;
+  char* base = (char*)scratch;
+  a.rows = (MaskRow*)base;
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t P = (uint32_t)(width * height), gx = (P + 255u) / 256u;
+  if (n_overlaps > 0) {
+    ProfScope ps__("tracking_mask_fold", st);
+    hipLaunchKernelGGL(tracking_mask_fold, dim3(1), dim3(64), 0, st, a);
+  }
+  if (outlier) {
+    MedianScratch* ms = (MedianScratch*)(base + mask_rows_bytes(n_overlaps));
+    float* median = (float*)((char*)ms + align256(sizeof(MedianScratch)));
+    a.err = median + 64;
+    a.median = median;
+    {
+      ProfScope ps__("tracking_mask_error", st);
+      hipLaunchKernelGGL(tracking_mask_error, dim3(gx), dim3(256), 0, st, a);
+    }
+    const MedianSource src{a.err, nullptr, nullptr};
+    const int rc = median_passes(src, P, ms, st);
+    if (rc != VTGS_OK) return rc;
+    ProfScope ps__("lower_median_finish", st);
+    hipLaunchKernelGGL(lower_median_finish, dim3(1), dim3(256), 0, st, P, ms, median, (uint32_t*)nullptr);
+  }
+  {
+    ProfScope ps__("tracking_mask", st);
+    hipLaunchKernelGGL(tracking_mask, dim3(gx), dim3(256), 0, st, a, (const MaskRow*)a.rows);
+  }
+  VTGS_HIP(hipGetLastError());
+  return VTGS_OK;
+}
+
 int vtgs_profile_enable(int on) {
   g_prof_on = on != 0;
   g_prof_n = 0;

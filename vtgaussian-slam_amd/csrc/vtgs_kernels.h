@@ -160,6 +160,28 @@ __global__ void keyframe_mark_repeats(KeyframeArgs a);
 // `rows` = a.rows as a read-only, non-aliased kernel argument: the loop's row loads become scalar loads
 __global__ void keyframe_overlap(KeyframeArgs a, const KeyframeRow* __restrict__ rows);
 
+// ---- vtgs_masks.hip: visibility, far-depth and outlier-depth masks of the tracking loss in one pass ----------------------------
+struct alignas(16) MaskRow {                  // written by tracking_mask_fold for tracking_mask (uniform loads)
+  float m[12];                                // K W_j[:3,:] inverse(curr_w2c), row-major 3x4
+  uint32_t pad[4];
+};
+struct MaskArgs {
+  int W, H, n;                                // n = overlapping frames, 0..3 (0: no visibility mask)
+  const float* gt; const float* k; const float* curr_w2c;
+  const float* ov_w2c0; const float* ov_w2c1; const float* ov_w2c2;
+  const float* ov_depth0; const float* ov_depth1; const float* ov_depth2;
+  float thres; int use_far; float far;
+  const float* rendered;                      // plane 0 of the depth / silhouette render; NULL = no outlier mask
+  float* err;                                 // [H*W] scratch, NULL = no outlier mask
+  const float* median;                        // the lower median of err, in scratch
+  MaskRow* rows;                              // [3]
+  float* out; uint8_t* out_u8; uint8_t* out_bits;
+};
+__global__ void tracking_mask_fold(MaskArgs a);
+__global__ void tracking_mask_error(MaskArgs a);
+// `rows` = a.rows as a read-only, non-aliased kernel argument: the row loads become scalar loads
+__global__ void tracking_mask(MaskArgs a, const MaskRow* __restrict__ rows);
+
 // ---- the cross-check composites of the test-only libvtgs_xcheck.so (vtgs_xcheck_composites.hip, vtgs_composite_bq.hip) -------
 __global__ void composite_forward(
     CamScalars cs, const float* __restrict__ bg, uint32_t nblk,

@@ -22,6 +22,9 @@ Differences:
     a KeyError to the densification code.  `get_loss.SCREEN_SPACE_GRADIENT = True` (module attribute, or the environment
     variable VTGS_SCREEN_SPACE_GRADIENT=1) selects the two-render route -- `transform_to_frame` + the plain operator for the
     colour render with `means2D.retain_grad()`, the depth / silhouette render over the same bins -- and sets the real tensor;
+  * `get_loss.NATIVE_MASKS = True` (module attribute, or VTGS_NATIVE_MASKS=1; off by default) forms the visibility, far-depth
+    and outlier-depth masks with one native call (`losses.tracking_extra_mask`) instead of the torch operators: no host wait
+    in the iteration.  A visibility decision within float32 rounding of its threshold may then differ from the torch route;
   * `visualize_tracking_loss` is ignored (plots);
   * the entries of `weighted_losses` other than 'loss' are detached (the loops only log them).
 Unsupported argument combinations are rejected BEFORE `params` / `variables` are touched.  HIP only: no CPU path.
@@ -35,9 +38,10 @@ import torch
 from . import losses as _l
 from .fused import render_frame, render_frame_unfused
 
-__all__ = ["get_loss", "SCREEN_SPACE_GRADIENT"]
+__all__ = ["get_loss", "SCREEN_SPACE_GRADIENT", "NATIVE_MASKS"]
 
 SCREEN_SPACE_GRADIENT = os.environ.get("VTGS_SCREEN_SPACE_GRADIENT", "0") == "1"
+NATIVE_MASKS = os.environ.get("VTGS_NATIVE_MASKS", "0") == "1"
 
 
 class _NoScreenSpaceGradient:
@@ -120,23 +124,31 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
         thr = sil_thres
 
     # :523-588 -- detached masks beyond gt_depth > 0 & finite (those two live in the loss node)
-    masks = []
-    if ignore_outlier_depth_loss:
-        masks.append(_l.outlier_depth_mask(gt_depth, depth))
+    overlaps = []
     if tracking and overlap_w2c is not None and dataset_name != "replica":
         if dataset_name == "tum":
             overlaps = [(overlap_w2c, overlap_gtdepth)]
         elif dataset_name in ("scannet", "scannetpp"):
             overlaps = [(overlap_w2c, overlap_gtdepth), (overlap_mid_w2c, overlap_mid_gtdepth),
                         (overlap_last_w2c, overlap_last_gtdepth)]
-        else:
-            overlaps = []
-        masks.append(_l.visibility_mask(gt_depth, curr_data["intrinsics"], curr_w2c, overlaps, vis_mask_thres)[None])
-    if tracking and far_depth_filter_thres is not None and dataset_name not in ("replica", "scannetpp"):
-        masks.append(_l.far_depth_mask(gt_depth, far_depth_filter_thres))
+    use_vis = tracking and overlap_w2c is not None and dataset_name != "replica"
+    far = far_depth_filter_thres if (tracking and far_depth_filter_thres is not None
+                                     and dataset_name not in ("replica", "scannetpp")) else None
     extra = None
-    for m in masks:
-        extra = m if extra is None else (extra & m)
+    if NATIVE_MASKS and (ignore_outlier_depth_loss or use_vis or far is not None):
+        # one native call (vtgs_tracking_mask): no torch.where / host wait, the float mask the loss node reads as it is
+        extra = _l.tracking_extra_mask(gt_depth, curr_data["intrinsics"], curr_w2c, overlaps, vis_mask_thres, far,
+                                       depth if ignore_outlier_depth_loss else None)
+    else:
+        masks = []
+        if ignore_outlier_depth_loss:
+            masks.append(_l.outlier_depth_mask(gt_depth, depth))
+        if use_vis:
+            masks.append(_l.visibility_mask(gt_depth, curr_data["intrinsics"], curr_w2c, overlaps, vis_mask_thres)[None])
+        if far is not None:
+            masks.append(_l.far_depth_mask(gt_depth, far))
+        for m in masks:
+            extra = m if extra is None else (extra & m)
 
     # :681-689 -- bookkeeping, decided here because it rides in the loss's last launch when it can:
     # max_2D_radius[seen] = max(radius[seen], max_2D_radius[seen]) without the boolean-mask gathers (each of them waits for

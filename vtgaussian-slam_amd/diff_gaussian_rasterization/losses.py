@@ -10,7 +10,7 @@ import ctypes
 
 import torch
 
-from . import _I32, _P, _check, _lib, _stream_ptr
+from . import _I32, _P, _SZ, _check, _lib, _stream_ptr
 
 _lib.vtgs_ssim_partial_rows.restype, _lib.vtgs_ssim_partial_rows.argtypes = ctypes.c_uint32, [_I32, _I32, _I32]
 _lib.vtgs_ssim_forward.restype, _lib.vtgs_ssim_forward.argtypes = ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P]
@@ -326,6 +326,85 @@ def visibility_mask(gt_depth, intrinsics, curr_w2c, overlaps, vis_mask_thres: fl
         vis = (torch.abs(samp - pz[:, 0]) < vis_mask_thres * torch.minimum(samp, pz[:, 0])).reshape(H, W)
         out = vis if out is None else (out | vis)
     return out
+
+
+# ---- the same masks in one native pass (csrc/vtgs_masks.hip; vtgs_tracking_mask in include/vtgs.h) ----------------------
+_lib.vtgs_tracking_mask_scratch_bytes.restype, _lib.vtgs_tracking_mask_scratch_bytes.argtypes = _SZ, [_I32] * 4
+_lib.vtgs_tracking_mask.restype = ctypes.c_int
+_lib.vtgs_tracking_mask.argtypes = [_I32, _I32, _P, _P, _P, _I32, _P, _P, ctypes.c_float, _I32, ctypes.c_float, _P, _P, _SZ, _P, _P, _P,
+                                    _P]
+_mask_scratch = {}          # (device, H, W, overlaps, outlier) -> uint8 scratch tensor, reused by every call of that shape
+
+
+def _dev_f32(t, dev):
+    return torch.as_tensor(t).detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def tracking_extra_mask(gt_depth, intrinsics, curr_w2c, overlaps, vis_mask_thres: float = 0.05, far_depth_filter_thres=None,
+                        rendered_depth=None, return_parts: bool = False):
+    """`visibility_mask` (when `overlaps` is not empty) & `far_depth_mask` (when `far_depth_filter_thres` is not None) &
+    `outlier_depth_mask` (when `rendered_depth` [1,H,W] / [H,W], plane 0 of the depth / silhouette render, is given) as ONE
+    native call on the current stream: 2 launches for visibility alone, 8 with the outlier mask, no host wait, no
+    torch.where, no torch.inverse (the rigid inverse of `curr_w2c` is taken on the device).  Returns the float32 [1,H,W]
+    0 / 1 mask that `tracking_loss` / `mapping_loss` take as `extra_mask` without converting it.  `overlaps`: up to three
+    (w2c [4,4], gt depth [1,H,W]) pairs; `curr_w2c` may be None without overlaps.  With nothing requested the mask is all ones.
+    return_parts: (mask, the mask as bool [H,W], uint8 [H,W] with the visibility in overlap j in bit j).
+    A visibility decision within float32 rounding of its threshold may differ from `visibility_mask`; a pixel with
+    gt_depth < 0 or NaN has visibility 0 (the reference fails on such a frame).  HIP only: no CPU path."""
+    if not isinstance(gt_depth, torch.Tensor) or not gt_depth.is_cuda:
+        raise RuntimeError("tracking_extra_mask needs tensors on a HIP device (torch 'cuda'); no CPU path exists")
+    dev = gt_depth.device
+    gd = _dev_f32(gt_depth, dev)
+    H, W = gd.shape[-2], gd.shape[-1]
+    if gd.numel() != H * W:
+        raise ValueError("gt_depth must be [1,H,W] / [H,W]")
+    overlaps = list(overlaps) if overlaps is not None else []
+    n = len(overlaps)
+    if n > 3:
+        raise ValueError("at most three overlapping frames")
+    k = pose = wp = dp = None
+    keep = []
+    if n:
+        if curr_w2c is None:
+            raise ValueError("curr_w2c is needed with overlapping frames")
+        k = _dev_f32(intrinsics, dev)[:3, :3].contiguous()
+        pose = _dev_f32(curr_w2c, dev).reshape(16)
+        ws = [_dev_f32(w, dev).reshape(16) for w, _ in overlaps]
+        ds = [_dev_f32(d, dev) for _, d in overlaps]
+        if any(d.numel() != H * W for d in ds):
+            raise ValueError("every overlap depth must hold H*W values")
+        keep = ws + ds
+        wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in ws])
+        dp = (ctypes.c_void_p * n)(*[d.data_ptr() for d in ds])
+    rd = None
+    if rendered_depth is not None:
+        rd = _dev_f32(rendered_depth, dev)
+        if rd.numel() != H * W:
+            raise ValueError("rendered_depth must be [1,H,W] / [H,W] (plane 0 of the depth / silhouette render)")
+    key = (dev, H, W, n, rd is not None)
+    scratch = _mask_scratch.get(key)
+    if scratch is None:
+        sbytes = int(_lib.vtgs_tracking_mask_scratch_bytes(W, H, n, 1 if rd is not None else 0))
+        scratch = _mask_scratch[key] = torch.empty(max(sbytes, 16), dtype=torch.uint8, device=dev)
+    out = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    u8 = torch.empty((H, W), dtype=torch.uint8, device=dev) if return_parts else None
+    bits = torch.empty((H, W), dtype=torch.uint8, device=dev) if return_parts else None
+    p = lambda t: None if t is None else t.data_ptr()
+    _check(_lib.vtgs_tracking_mask(W, H, gd.data_ptr(), p(k), p(pose), n, wp, dp, float(vis_mask_thres),
+                                   0 if far_depth_filter_thres is None else 1,
+                                   0.0 if far_depth_filter_thres is None else float(far_depth_filter_thres), p(rd),
+                                   scratch.data_ptr(), scratch.numel(), out.data_ptr(), p(u8), p(bits), _stream_ptr(dev)),
+           "vtgs_tracking_mask")
+    del keep
+    return (out, u8.view(torch.bool), bits) if return_parts else out
+
+
+def visibility_mask_native(gt_depth, intrinsics, curr_w2c, overlaps, vis_mask_thres: float = 0.05):
+    """`visibility_mask` through vtgs_tracking_mask: same arguments, [H,W] bool on gt_depth's device (None without
+    overlapping frames, as there), two launches and no host wait."""
+    if not len(overlaps):
+        return None
+    return tracking_extra_mask(gt_depth, intrinsics, curr_w2c, overlaps, vis_mask_thres, return_parts=True)[1]
 
 
 _lib.vtgs_silhouette_sweep.restype = ctypes.c_int
