@@ -481,7 +481,8 @@ int vtgs_slam_loss_forward(int32_t mode, const float* im, const float* depth_sil
                            void* stream);
 /* The same, with get_loss's bookkeeping of the render it belongs to (src/vtgaussian_slam.py:681-689: seen = radius > 0, the
  * running maximum of the screen-space radius) in the SAME launch as the loss's last step -- vtgs_seen_and_max_radius folded in:
- * one launch less per iteration.  n = 0: exactly vtgs_slam_loss_forward.  radii / max_2d_radius 16-byte aligned.  (ABI 16) */
+ * one launch less per iteration.  n = 0: exactly vtgs_slam_loss_forward.  radii / max_2d_radius 16-byte aligned, seen 4-byte
+ * aligned (as vtgs_seen_and_max_radius below; VTGS_ERR_INVALID_ARGUMENT otherwise, nothing launched).  (ABI 16)       */
 int vtgs_slam_loss_forward_seen(int32_t mode, const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth,
                                 int32_t height, int32_t width, float sil_thres, float w_im, float w_depth, float* scratch,
                                 float* ssim_grad_maps, float* out8, const float* extra_mask, const float* color_weight,
@@ -550,7 +551,10 @@ int vtgs_adam_step_rows(const VtgsAdamGroup* groups, int32_t n_groups, int32_t s
 /* The bookkeeping at the end of get_loss (src/vtgaussian_slam.py:681-689) in one launch instead of three element-wise ones:
  *   seen[i] = radii[i] > 0;   max_2D_radius[i] = max(max_2D_radius[i], (float)radii[i])   (a culled Gaussian has radius 0 and
  *   the running maximum is never negative, so the unmasked maximum equals the reference's masked update).
- * radii[N] int32 (the operator's second output), max_2d_radius[N] float32 in place, seen[N] one byte per Gaussian (0 / 1). */
+ * radii[N] int32 (the operator's second output), max_2d_radius[N] float32 in place, seen[N] one byte per Gaussian (0 / 1).
+ * The kernel moves four Gaussians per thread (int4 / float4 loads, four `seen` bytes as one 32-bit store) and has no scalar
+ * fallback: radii and max_2d_radius must be 16-byte aligned and seen 4-byte aligned (every torch allocation is).  With N > 0
+ * anything else is refused with VTGS_ERR_INVALID_ARGUMENT before any device work; the buffers are left as they were.     */
 int vtgs_seen_and_max_radius(int32_t n, const int32_t* radii, float* max_2d_radius, uint8_t* seen, void* stream);
 
 /* ---- Point-to-plane consistency of two depth frames -----------------------------------------------

@@ -694,9 +694,16 @@ int vtgs_adam_step_rows(const VtgsAdamGroup* groups, int32_t n_groups, int32_t s
   return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
 }
 
+// seen_and_max_radius_block has no scalar fallback: radii / max_2d_radius are read as int4 / float4 and four `seen` bytes are
+// stored as one uint32_t, so both entry points refuse pointers that are not aligned for that before any device work
+static bool bookkeeping_aligned(const int32_t* radii, const float* max_2d_radius, const uint8_t* seen) {
+  return (((uintptr_t)radii | (uintptr_t)max_2d_radius) & 15u) == 0u && ((uintptr_t)seen & 3u) == 0u;
+}
+
 int vtgs_seen_and_max_radius(int32_t n, const int32_t* radii, float* max_2d_radius, uint8_t* seen, void* stream) {
   if (n < 0 || (n > 0 && (!radii || !max_2d_radius || !seen))) return VTGS_ERR_INVALID_ARGUMENT;
   if (n == 0) return VTGS_OK;
+  if (!bookkeeping_aligned(radii, max_2d_radius, seen)) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(seen_and_max_radius_kernel, dim3((uint32_t)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, n, radii,
                      max_2d_radius, seen);
   return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
@@ -755,7 +762,7 @@ int vtgs_slam_loss_forward_seen(int32_t mode, const float* im, const float* dept
   if ((mode < 0 || mode > 2) || !im || !depth_sil || !gt_im || !gt_depth || !scratch || !out5 || height <= 0 || width <= 0)
     return VTGS_ERR_INVALID_ARGUMENT;
   if (n < 0 || (n > 0 && (!radii || !max_2d_radius || !seen))) return VTGS_ERR_INVALID_ARGUMENT;
-  if (n > 0 && (((uintptr_t)radii | (uintptr_t)max_2d_radius) & 15u)) return VTGS_ERR_INVALID_ARGUMENT;   // (read as int4 / float4)
+  if (n > 0 && !bookkeeping_aligned(radii, max_2d_radius, seen)) return VTGS_ERR_INVALID_ARGUMENT;
   const int32_t P = height * width;
   const uint32_t l1_rows = vtgs_masked_l1_partial_rows(P);
   float* ssim_partial = scratch + (size_t)l1_rows * 3;
