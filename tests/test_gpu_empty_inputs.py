@@ -20,6 +20,7 @@ from parity_util import to_settings
 
 pytestmark = pytest.mark.gpu
 NULL = None
+INVALID_ARGUMENT = 1          # include/vtgs.h: VTGS_ERR_INVALID_ARGUMENT
 
 
 def _call(lib, name, *args, what=None):
@@ -172,3 +173,56 @@ def test_empty_map_through_the_operator_and_the_fused_frame(gpu_device, ext, mon
         assert all(v.grad is None or v.grad.numel() == 0 for v in leaves.values())
     finally:
         dgr.poison_workspaces(False)
+
+
+def test_status_of_the_frame_loss_point2plane_and_sh_entry_points(gpu_device):
+    """include/vtgs.h promises a message behind vtgs_last_hip_error() for every VTGS_ERR_HIP.  The entry points of
+    csrc/vtgs_frame.hip, vtgs_loss.hip, vtgs_p2p.hip and vtgs_sh.hip now end in the same status call as the rest of the
+    library.  What can be checked without making a HIP call fail: one entry point of each file returns VTGS_OK after a small
+    valid launch (and the launch did its work), VTGS_ERR_INVALID_ARGUMENT for bad arguments as before, and neither writes a
+    HIP message."""
+    import diff_gaussian_rasterization as dgr
+    from diff_gaussian_rasterization import fused, losses, point2plane, surface   # noqa: F401  (their ctypes signatures)
+    lib, dev = dgr._lib, gpu_device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    before = lib.vtgs_last_hip_error()
+    g = torch.Generator().manual_seed(2)
+    # csrc/vtgs_frame.hip
+    rots, trans = torch.rand(1, 4, 3, generator=g).to(dev), torch.rand(1, 3, 3, generator=g).to(dev)
+    pose7 = torch.full((7,), float("nan"), device=dev)
+    _call(lib, "vtgs_pose_slot_gather", rots.data_ptr(), trans.data_ptr(), 3, 1, pose7.data_ptr(), stream)
+    assert torch.equal(pose7[:4], rots[0, :, 1]) and torch.equal(pose7[4:], trans[0, :, 1])
+    assert lib.vtgs_pose_slot_gather(rots.data_ptr(), trans.data_ptr(), 3, 3, pose7.data_ptr(), stream) == INVALID_ARGUMENT
+    # csrc/vtgs_loss.hip
+    P = 40 * 24
+    im, ds, gt_im = (torch.rand(3, 24, 40, generator=g).to(dev) for _ in range(3))
+    gt_d = torch.rand(1, 24, 40, generator=g).to(dev)
+    partial = torch.full((int(lib.vtgs_masked_l1_partial_rows(P)), 3), float("nan"), device=dev)
+    g_im, g_ds = torch.empty_like(im), torch.empty_like(ds)
+    args = (im.data_ptr(), ds.data_ptr(), gt_im.data_ptr(), gt_d.data_ptr(), P, 0.5)
+    _call(lib, "vtgs_masked_l1", *args, 0, partial.data_ptr(), g_im.data_ptr(), g_ds.data_ptr(), stream)
+    assert bool(torch.isfinite(partial).all())
+    assert lib.vtgs_masked_l1(*args, 3, partial.data_ptr(), g_im.data_ptr(), g_ds.data_ptr(), stream) == INVALID_ARGUMENT
+    # csrc/vtgs_p2p.hip
+    W, H = 40, 24
+    depth = (1.0 + torch.rand(H, W, generator=g)).to(dev)
+    k = torch.tensor([[30.0, 0, 19.5], [0, 30.0, 11.5], [0, 0, 1]], device=dev)
+    w2c = torch.eye(4, device=dev).reshape(16)
+    sbytes = int(lib.vtgs_point2plane_scratch_bytes(W, H))
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+    dist, matched = torch.full((H, W), float("nan"), device=dev), torch.empty((H, W), dtype=torch.uint8, device=dev)
+    args = (W, H, depth.data_ptr(), depth.data_ptr(), NULL, NULL, k.data_ptr(), w2c.data_ptr(), w2c.data_ptr())
+    _call(lib, "vtgs_point2plane", *args, 0.02, 1, scratch.data_ptr(), sbytes, dist.data_ptr(), matched.data_ptr(), stream)
+    assert bool(torch.isfinite(dist).all())
+    assert lib.vtgs_point2plane(*args, 0.0, 1, scratch.data_ptr(), sbytes, dist.data_ptr(), matched.data_ptr(), stream) \
+        == INVALID_ARGUMENT
+    # csrc/vtgs_sh.hip
+    n = 300
+    means, shs = torch.randn(n, 3, generator=g).to(dev), torch.randn(n, 4, 3, generator=g).to(dev)
+    campos = torch.zeros(3, device=dev)
+    colors, clamped = torch.full((n, 3), float("nan"), device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    args = (means.data_ptr(), campos.data_ptr(), shs.data_ptr(), colors.data_ptr(), clamped.data_ptr(), stream)
+    _call(lib, "vtgs_sh_forward", n, 1, 4, *args)
+    assert bool(torch.isfinite(colors).all())
+    assert lib.vtgs_sh_forward(n, 2, 4, *args) == INVALID_ARGUMENT          # degree 2 needs nine coefficients
+    assert lib.vtgs_last_hip_error() == before

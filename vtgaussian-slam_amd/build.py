@@ -18,7 +18,7 @@ SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_api.hip", "vtgs_binning.hip
 # implementation switch asks
 XCHECK_SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_xcheck.hip", "vtgs_xcheck_composites.hip", "vtgs_composite_bq.hip")]
 HDR = [os.path.join(HERE, "csrc", f) for f in ("vtgs_internal.h", "vtgs_math.h", "vtgs_kernels.h", "vtgs_composite_common.h",
-                                               "vtgs_composite_backward.h", "vtgs_sort_common.h")] + \
+                                               "vtgs_composite_backward.h", "vtgs_sort_common.h", "vtgs_host.h")] + \
       [os.path.join(HERE, "..", "include", "vtgs.h")]
 OUT = os.path.join(HERE, "lib", "libvtgs.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

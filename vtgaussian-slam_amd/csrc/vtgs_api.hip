@@ -1,12 +1,15 @@
 // vtgs_api.hip -- the extern "C" surface declared in include/vtgs.h: argument checks, workspace carving,
 // kernel launches on the caller's stream.  No device allocation, no retained pointers.
 #include "../../include/vtgs.h"
+#include "vtgs_host.h"
 #include "vtgs_internal.h"
 #include "vtgs_kernels.h"
 
 #include <dlfcn.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include <algorithm>
 #include <mutex>
 #include <string>
@@ -19,18 +22,6 @@ __global__ void uniform_plan_kernel(uint32_t* plan, uint32_t entries, uint32_t s
 }  // namespace vtgs
 
 using namespace vtgs;
-
-static thread_local char g_hip_err[256] = "";
-
-static int hip_fail(hipError_t e, const char* what) {
-  snprintf(g_hip_err, sizeof(g_hip_err), "%s: %s", what, hipGetErrorString(e));
-  return VTGS_ERR_HIP;
-}
-#define VTGS_HIP(call)                                        \
-  do {                                                        \
-    hipError_t e__ = (call);                                  \
-    if (e__ != hipSuccess) return hip_fail(e__, #call);       \
-  } while (0)
 
 // ---- the cross-check composites (scalar, quad form, lane = pixel forward, quadrant-queue backward) are NOT in this library:
 // they live in the test-only libvtgs_xcheck.so (csrc/vtgs_xcheck.hip), opened next to this library the first time an
@@ -140,57 +131,19 @@ static CamScalars scalars_of(const VtgsCamera* cam, int row8_begin, int row8_end
   return cs;
 }
 
-extern "C" {
+// ---- everything the entry points share; only what include/vtgs.h declares sits in the extern "C" block below -----------------
+namespace {
 
-uint32_t vtgs_abi_version(void) { return VTGS_ABI_VERSION; }
-
-const char* vtgs_strerror(int status) {
-  switch (status) {
-    case VTGS_OK: return "ok";
-    case VTGS_ERR_INVALID_ARGUMENT: return "invalid argument";
-    case VTGS_ERR_WORKSPACE_TOO_SMALL: return "workspace too small";
-    case VTGS_ERR_INSTANCE_OVERFLOW: return "more (Gaussian,tile) instances than instance_capacity or a tile list longer than tile_capacity";
-    case VTGS_ERR_HIP: return "HIP runtime error";
-    case VTGS_ERR_STALE_WORKSPACE: return "workspace holds no completed forward for these sizes";
-    default: return "unknown status";
-  }
-}
-
-const char* vtgs_last_hip_error(void) { return g_hip_err; }
-
-size_t vtgs_workspace_bytes(int32_t n, int32_t width, int32_t height, uint64_t instance_capacity, uint32_t tile_capacity) {
-  if (n < 0 || width <= 0 || height <= 0 || (tile_capacity & ~VTGS_TILE_CAPACITY_PLANNED) == 0) return 0;
-  return make_layout(n, width, height, instance_capacity, tile_capacity).total;
-}
-
-size_t vtgs_workspace_clear_bytes(int32_t image_width, int32_t image_height) {
-  if (image_width <= 0 || image_height <= 0) return 0;
-  const size_t tiles8 = (size_t)((image_width + kSubTile - 1) / kSubTile) * (size_t)((image_height + kSubTile - 1) / kSubTile);
-  return 256 + align256((tiles8 + 1) * 4);       // WsLayout: counters at byte 0, tile_cnt behind them
-}
-
-size_t vtgs_backward_scratch_bytes(int32_t n, uint64_t instances) {
-  (void)n;
-  return align256((size_t)(instances ? instances : 1) * kGradRec * sizeof(float));
-}
-
-size_t vtgs_backward_dual_scratch_bytes(int32_t n, uint64_t instances) {
-  (void)n;
-  return align256((size_t)(instances ? instances : 1) * kGradRecDual * sizeof(float));
-}
-
-#include <stdlib.h>
-#include <time.h>
 // Implementation switches: defaults from the environment, read once; vtgs_set_option overrides them at run time.
 struct Option { const char* name; int dflt; int value; };
-static Option g_options[] = {{"VTGS_FWD_IMPL", 3, -1}, {"VTGS_BWD_IMPL", 2, -1}, {"VTGS_BIN_IMPL", 1, -1}, {"VTGS_SORT_PACKED", 1, -1},
+Option g_options[] = {{"VTGS_FWD_IMPL", 3, -1}, {"VTGS_BWD_IMPL", 2, -1}, {"VTGS_BIN_IMPL", 1, -1}, {"VTGS_SORT_PACKED", 1, -1},
                              {"VTGS_SORT_FUSED", 1, -1}, {"VTGS_COUNT_STEPS", 0, -1}, {"VTGS_SORT_LONG_COUNTING", 1, -1},
                              {"VTGS_DUAL_B1", 1, -1},    // 0: ignore frame flag 8 (the full dual backward: the cross-check of the one-channel form)
                              {"VTGS_DEPTH_LITE", 1, -1}}; // 0: ignore VTGS_FORWARD_SECOND_IS_DEPTH (the full dual forward)
 enum { OPT_FWD_IMPL = 0, OPT_BWD_IMPL, OPT_BIN_IMPL, OPT_SORT_PACKED, OPT_SORT_FUSED, OPT_COUNT_STEPS, OPT_SORT_LONG_COUNTING, OPT_DUAL_B1,
        OPT_DEPTH_LITE, OPT_COUNT };
-static std::once_flag g_options_once;
-static void options_init() {                                   // thread-safe: the first caller reads the environment
+std::once_flag g_options_once;
+void options_init() {                                   // thread-safe: the first caller reads the environment
   std::call_once(g_options_once, [] {
     for (int i = 0; i < OPT_COUNT; ++i) {
       const char* v = getenv(g_options[i].name);
@@ -199,24 +152,47 @@ static void options_init() {                                   // thread-safe: t
     }
   });
 }
-static inline int option(int which) { options_init(); return g_options[which].value; }
-int vtgs_set_option(const char* name, int value) {
-  options_init();
-  if (!name) return VTGS_ERR_INVALID_ARGUMENT;
-  for (int i = 0; i < OPT_COUNT; ++i)
-    if (strcmp(name, g_options[i].name) == 0) { g_options[i].value = value < 0 ? g_options[i].dflt : value; return VTGS_OK; }
-  return VTGS_ERR_INVALID_ARGUMENT;
+int option(int which) { options_init(); return g_options[which].value; }
+
+// ---- which instantiation runs.  Every instantiation of a kernel template that this file launches is named HERE and nowhere
+// else in the host code; each launch below goes through the chosen pointer, so its argument list is written once.  All
+// instantiations of a template have the function type that csrc/vtgs_kernels.h declares, and the arguments convert through it.
+using ProjectKernel = decltype(&project_and_bin<0, 0>);
+using DeferredKernel = decltype(&bin_deferred_splats<false>);
+using ForwardKernel = decltype(&composite_forward_q<0>);
+using BackwardKernel = decltype(&composite_backward_mx<4, false, true, false>);
+using GatherKernel = decltype(&gather_splat_grads<false, false, false, false>);
+using MedianKernel = decltype(&lower_median_pass<0>);
+
+// [LDS][MODE].  LDS: 0 = run-aggregated global atomics, 1 = the band's whole tile table in LDS, 2 = a window of kWinEntries
+// tiles.  MODE: bit 0 = a band of tile rows, bit 1 = planned bins, bit 2 = cov3D (never with planned bins: forward_impl's
+// argument check).  The windowed form has no cov3D instantiation: a null entry is not launched.
+const ProjectKernel kProjectKernels[3][6] = {
+    {project_and_bin<0, 0>, project_and_bin_capped<0, 1>, project_and_bin_capped<0, 2>, project_and_bin_capped<0, 3>,
+     project_and_bin_capped<0, 4>, project_and_bin_capped<0, 5>},
+    {project_and_bin<1, 0>, project_and_bin_capped<1, 1>, project_and_bin_capped<1, 2>, project_and_bin_capped<1, 3>,
+     project_and_bin_capped<1, 4>, project_and_bin_capped<1, 5>},
+    {project_and_bin<2, 0>, project_and_bin_capped<2, 1>, project_and_bin_capped<2, 2>, project_and_bin_capped<2, 3>,
+     nullptr, nullptr}};
+const DeferredKernel kDeferredKernels[2] = {bin_deferred_splats<false>, bin_deferred_splats<true>};            // [PLANNED]
+// [MODE]: 0 = single render (colour + depth), 1 = dual render, 2 = dual render whose second set is [z, 1, z^2]
+const ForwardKernel kForwardKernels[3] = {composite_forward_q<0>, composite_forward_q<1>, composite_forward_q<2>};
+const struct { MedianKernel kernel; const char* profile_name; } kMedianPasses[3] = {
+    {lower_median_pass<0>, "lower_median_pass0"}, {lower_median_pass<1>, "lower_median_pass1"}, {lower_median_pass<2>, "lower_median_pass2"}};
+
+// lane = pixel replay (the default backward); b1: the one-channel form of the dual render's second gradient
+BackwardKernel backward_kernel(bool dual, bool b1) {
+  if (b1) return composite_backward_mx<4, true, true, true>;
+  return dual ? composite_backward_mx<4, true, true, false> : composite_backward_mx<4, false, true, false>;
 }
-int vtgs_get_option(const char* name) {
-  options_init();
-  if (!name) return -1;
-  for (int i = 0; i < OPT_COUNT; ++i)
-    if (strcmp(name, g_options[i].name) == 0) return g_options[i].value;
-  return -1;
+GatherKernel gather_kernel(bool dual, bool frame, bool cov3d, bool b1) {      // <DUAL, FRAME, COV3D, B1>
+  if (b1) return gather_splat_grads<true, true, false, true>;
+  if (dual) return frame ? gather_splat_grads<true, true, false, false> : gather_splat_grads<true, false, false, false>;
+  return cov3d ? gather_splat_grads<false, false, true, false> : gather_splat_grads<false, false, false, false>;
 }
 
 // colors_b / out_color_b != NULL: dual render (two colour sets over the same geometry, no depth image)
-static int launch_composite_forward(const VtgsCamera* cam, const CamScalars& cs, int rows16, const WsLayout& L,
+int launch_composite_forward(const VtgsCamera* cam, const CamScalars& cs, int rows16, const WsLayout& L,
                                     char* ws, const float* colors, float* out_color, float* out_depth,
                                     float* image_state, hipStream_t st, const float* colors_b = nullptr,
                                     float* out_color_b = nullptr, int sort_mode = 0, FinalizeArgs fin = FinalizeArgs{},
@@ -236,28 +212,16 @@ static int launch_composite_forward(const VtgsCamera* cam, const CamScalars& cs,
                                                            // matrix-core kernel, 0 = scalar kernel (read per call)
   {
     ProfScope ps__(dual ? "composite_forward_dual" : "composite_forward", st);
-    if (impl == 3 && dual && second_is_depth)               // the single render's kernel with z in its depth column (see the kernel)
-      hipLaunchKernelGGL((composite_forward_q<2>), dim3(nblk), dim3(256), 0, st, cs, cam->bg, nblk,
+    if (impl == 3) {                                        // quadrant queues (vtgs_composite_q.hip)
+      // MODE 2: the single render's kernel with z in its depth column (see the kernel)
+      const ForwardKernel forward_kernel = kForwardKernels[!dual ? 0 : (second_is_depth ? 2 : 1)];
+      hipLaunchKernelGGL(forward_kernel, dim3(nblk), dim3(256), 0, st, cs, cam->bg, nblk,
                          (const uint32_t*)(ws + L.tile_cnt), L.tile_cap, (uint32_t*)(ws + L.sorted_gid),
-                         (const GeomRec*)(ws + L.geom), colors, out_color, (float*)nullptr, image_state,
-                         (const Counters*)(ws + L.counters), colors_b, out_color_b, sort_mode,
+                         (const GeomRec*)(ws + L.geom), colors, out_color, dual ? nullptr : out_depth, image_state,
+                         (const Counters*)(ws + L.counters), dual ? colors_b : nullptr, dual ? out_color_b : nullptr, sort_mode,
                          (const unsigned long long*)(ws + L.keys), (const uint32_t*)(ws + L.vals), (uint32_t*)(ws + L.sorted_inst), fin,
-                         write_qmask ? (uint8_t*)(ws + L.qmask) : (uint8_t*)nullptr, steps);
-    else if (impl == 3 && dual)                             // quadrant queues (vtgs_composite_q.hip)
-      hipLaunchKernelGGL((composite_forward_q<1>), dim3(nblk), dim3(256), 0, st, cs, cam->bg, nblk,
-                         (const uint32_t*)(ws + L.tile_cnt), L.tile_cap, (uint32_t*)(ws + L.sorted_gid),
-                         (const GeomRec*)(ws + L.geom), colors, out_color, (float*)nullptr, image_state,
-                         (const Counters*)(ws + L.counters), colors_b, out_color_b, sort_mode,
-                         (const unsigned long long*)(ws + L.keys), (const uint32_t*)(ws + L.vals), (uint32_t*)(ws + L.sorted_inst), fin,
-                         write_qmask ? (uint8_t*)(ws + L.qmask) : (uint8_t*)nullptr, steps);
-    else if (impl == 3)
-      hipLaunchKernelGGL((composite_forward_q<0>), dim3(nblk), dim3(256), 0, st, cs, cam->bg, nblk,
-                         (const uint32_t*)(ws + L.tile_cnt), L.tile_cap, (uint32_t*)(ws + L.sorted_gid),
-                         (const GeomRec*)(ws + L.geom), colors, out_color, out_depth, image_state,
-                         (const Counters*)(ws + L.counters), (const float*)nullptr, (float*)nullptr, sort_mode,
-                         (const unsigned long long*)(ws + L.keys), (const uint32_t*)(ws + L.vals), (uint32_t*)(ws + L.sorted_inst), fin,
-                         write_qmask ? (uint8_t*)(ws + L.qmask) : (uint8_t*)nullptr, steps);
-    else {                                                  // a cross-check implementation: the test-only library
+                         write_qmask ? (uint8_t*)(ws + L.qmask) : nullptr, steps);
+    } else {                                                // a cross-check implementation: the test-only library
       if (!xcheck_available()) return xcheck_missing();
       const int rc = g_xcheck_forward(impl, dual ? 1 : 0, &cs, cam->bg, nblk, (const uint32_t*)(ws + L.tile_cnt), L.tile_cap,
                                       (const uint32_t*)(ws + L.sorted_gid), (const GeomRec*)(ws + L.geom), colors, out_color,
@@ -270,7 +234,7 @@ static int launch_composite_forward(const VtgsCamera* cam, const CamScalars& cs,
   return VTGS_OK;
 }
 
-static int forward_impl(const VtgsCamera* cam, int32_t n, const float* means3D, const float* colors, const float* colors_b,
+int forward_impl(const VtgsCamera* cam, int32_t n, const float* means3D, const float* colors, const float* colors_b,
                         const float* opacities, const float* scales, const float* rotations, float* out_color,
                         float* out_depth, float* out_color_b, int32_t* out_radii, void* workspace, size_t workspace_bytes,
                         uint64_t instance_capacity, uint32_t tile_capacity, VtgsForwardInfo* info, uint32_t flags,
@@ -340,61 +304,28 @@ static int forward_impl(const VtgsCamera* cam, int32_t n, const float* means3D, 
       int dev_id = 0;
       if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) { (void)hipGetLastError(); dev_id = -1; }
       if (dev_id < 0 || !raised[dev_id]) {
-        if (hipFuncSetAttribute((const void*)project_and_bin<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10) == hipSuccess &&
-            hipFuncSetAttribute((const void*)project_and_bin_capped<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10) == hipSuccess &&
-            hipFuncSetAttribute((const void*)project_and_bin_capped<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10) == hipSuccess &&
-            hipFuncSetAttribute((const void*)project_and_bin_capped<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10) == hipSuccess &&
-            hipFuncSetAttribute((const void*)project_and_bin_capped<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10) == hipSuccess &&
-            hipFuncSetAttribute((const void*)project_and_bin_capped<1, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10) == hipSuccess) {
+        bool all_raised = true;                               // (the LDS-table row of the one table: no second list to keep in step)
+        for (const ProjectKernel k : kProjectKernels[1])
+          all_raised = all_raised && (!k || hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10) == hipSuccess);
+        if (all_raised) {
           if (dev_id >= 0) raised[dev_id] = true;
         } else { (void)hipGetLastError(); lds_bins = false; }
       }
     }
+    const int lds = lds_bins ? 1 : (win_bins ? 2 : 0);
+    const int mode = ((r8b > 0 || r8e < (cam->image_height + kSubTile - 1) / kSubTile) ? 1 : 0) | (L.planned ? 2 : 0) | (cov3d ? 4 : 0);
+    const ProjectKernel project_kernel = kProjectKernels[lds][mode];
+    if (!project_kernel) return VTGS_ERR_INVALID_ARGUMENT;      // (windowed x cov3D: win_bins excludes it)
+    const size_t project_lds_bytes = lds == 1 ? table_bytes : (lds == 2 ? (size_t)(64u << 10) : 0);
+    if (mode == 0 && (flags & VTGS_FORWARD_EXPECT_NO_DEFERRED)) { cs.no_defer = 1u; no_defer = true; }   // (the hint: whole frame, uniform bins)
     {
       ProfScope ps__("project_and_bin", st);
-      const int mode = ((r8b > 0 || r8e < (cam->image_height + kSubTile - 1) / kSubTile) ? 1 : 0) | (L.planned ? 2 : 0) | (cov3d ? 4 : 0);
-      if (mode == 0 && (flags & VTGS_FORWARD_EXPECT_NO_DEFERRED)) { cs.no_defer = 1u; no_defer = true; }   // (the hint: whole frame, uniform bins)
-#define VTGS_LAUNCH_PROJECT(LDS, MODE, SHMEM)                                                                          \
-      hipLaunchKernelGGL((VTGS_PROJECT_KERNEL(LDS, MODE)), dim3((n + 1023) / 1024), dim3(1024), SHMEM, st, cs,             \
-                         cam->viewmatrix, cam->projmatrix, n, means3D, opacities, scales, rotations, out_radii,         \
-                         (GeomRec*)(ws + L.geom), (GaussAux*)(ws + L.gaux), (uint32_t*)(ws + L.tile_cnt),              \
-                         (unsigned long long*)(ws + L.keys), (uint32_t*)(ws + L.vals), ctr,                            \
-                         (BlockStats*)(ws + L.block_stats), (unsigned long long)instance_capacity, L.tile_cap,            \
-                         (DeferRec*)(ws + L.defer_list))
-      // (LDS: 0 = run-aggregated global atomics, 1 = the band's whole tile table in LDS, 2 = a window of kWinEntries tiles)
-      if (lds_bins) {
-#define VTGS_PROJECT_KERNEL(LDS, MODE) project_and_bin<LDS, MODE>
-        if (mode == 0) VTGS_LAUNCH_PROJECT(1, 0, table_bytes);
-#undef VTGS_PROJECT_KERNEL
-#define VTGS_PROJECT_KERNEL(LDS, MODE) project_and_bin_capped<LDS, MODE>
-        else if (mode == 1) VTGS_LAUNCH_PROJECT(1, 1, table_bytes);
-        else if (mode == 2) VTGS_LAUNCH_PROJECT(1, 2, table_bytes);
-        else if (mode == 4) VTGS_LAUNCH_PROJECT(1, 4, table_bytes);
-        else if (mode == 5) VTGS_LAUNCH_PROJECT(1, 5, table_bytes);
-        else VTGS_LAUNCH_PROJECT(1, 3, table_bytes);
-      } else if (win_bins) {
-#undef VTGS_PROJECT_KERNEL
-#define VTGS_PROJECT_KERNEL(LDS, MODE) project_and_bin<LDS, MODE>
-        if (mode == 0) VTGS_LAUNCH_PROJECT(2, 0, (size_t)(64u << 10));
-#undef VTGS_PROJECT_KERNEL
-#define VTGS_PROJECT_KERNEL(LDS, MODE) project_and_bin_capped<LDS, MODE>
-        else if (mode == 1) VTGS_LAUNCH_PROJECT(2, 1, (size_t)(64u << 10));
-        else if (mode == 2) VTGS_LAUNCH_PROJECT(2, 2, (size_t)(64u << 10));
-        else VTGS_LAUNCH_PROJECT(2, 3, (size_t)(64u << 10));
-      } else {
-#undef VTGS_PROJECT_KERNEL
-#define VTGS_PROJECT_KERNEL(LDS, MODE) project_and_bin<LDS, MODE>
-        if (mode == 0) VTGS_LAUNCH_PROJECT(0, 0, 0);
-#undef VTGS_PROJECT_KERNEL
-#define VTGS_PROJECT_KERNEL(LDS, MODE) project_and_bin_capped<LDS, MODE>
-        else if (mode == 1) VTGS_LAUNCH_PROJECT(0, 1, 0);
-        else if (mode == 2) VTGS_LAUNCH_PROJECT(0, 2, 0);
-        else if (mode == 4) VTGS_LAUNCH_PROJECT(0, 4, 0);
-        else if (mode == 5) VTGS_LAUNCH_PROJECT(0, 5, 0);
-        else VTGS_LAUNCH_PROJECT(0, 3, 0);
-      }
-#undef VTGS_PROJECT_KERNEL
-#undef VTGS_LAUNCH_PROJECT
+      hipLaunchKernelGGL(project_kernel, dim3((n + 1023) / 1024), dim3(1024), project_lds_bytes, st, cs,
+                         cam->viewmatrix, cam->projmatrix, n, means3D, opacities, scales, rotations, out_radii,
+                         (GeomRec*)(ws + L.geom), (GaussAux*)(ws + L.gaux), (uint32_t*)(ws + L.tile_cnt),
+                         (unsigned long long*)(ws + L.keys), (uint32_t*)(ws + L.vals), ctr,
+                         (BlockStats*)(ws + L.block_stats), (unsigned long long)instance_capacity, L.tile_cap,
+                         (DeferRec*)(ws + L.defer_list));
     }
     VTGS_HIP(hipGetLastError());
     if (!no_defer) {
@@ -404,14 +335,9 @@ static int forward_impl(const VtgsCamera* cam, int32_t n, const float* means3D, 
       ProfScope ps__("bin_deferred_splats", st);
       const uint32_t lgrid = (uint32_t)min((long long)1024, max((long long)16, (long long)n / 1024));
       const uint32_t dgrid = lgrid + (uint32_t)min((long long)4096, max((long long)64, ((long long)n / 8 + 63) / 64));
-      if (L.planned)
-        hipLaunchKernelGGL((bin_deferred_splats<true>), dim3(dgrid), dim3(256), 0, st, cs, (GaussAux*)(ws + L.gaux), (uint32_t*)(ws + L.tile_cnt),
-                           (unsigned long long*)(ws + L.keys), (uint32_t*)(ws + L.vals), ctr, (const DeferRec*)(ws + L.defer_list),
-                           (uint32_t)n, (unsigned long long)instance_capacity, L.tile_cap, lgrid);
-      else
-        hipLaunchKernelGGL((bin_deferred_splats<false>), dim3(dgrid), dim3(256), 0, st, cs, (GaussAux*)(ws + L.gaux), (uint32_t*)(ws + L.tile_cnt),
-                           (unsigned long long*)(ws + L.keys), (uint32_t*)(ws + L.vals), ctr, (const DeferRec*)(ws + L.defer_list),
-                           (uint32_t)n, (unsigned long long)instance_capacity, L.tile_cap, lgrid);
+      hipLaunchKernelGGL(kDeferredKernels[L.planned ? 1 : 0], dim3(dgrid), dim3(256), 0, st, cs, (GaussAux*)(ws + L.gaux),
+                         (uint32_t*)(ws + L.tile_cnt), (unsigned long long*)(ws + L.keys), (uint32_t*)(ws + L.vals), ctr,
+                         (const DeferRec*)(ws + L.defer_list), (uint32_t)n, (unsigned long long)instance_capacity, L.tile_cap, lgrid);
     }
     VTGS_HIP(hipGetLastError());
   }
@@ -512,6 +438,185 @@ static int forward_impl(const VtgsCamera* cam, int32_t n, const float* means3D, 
   return host.overflow ? VTGS_ERR_INSTANCE_OVERFLOW : VTGS_OK;
 }
 
+int backward_impl(const VtgsCamera* cam, int32_t n, const float* means3D, const float* colors, const float* colors_b,
+                         const float* opacities, const float* scales, const float* rotations, const float* out_color,
+                         const float* out_color_b, const float* grad_color, const float* grad_color_b,
+                         const void* workspace, size_t workspace_bytes, uint64_t instance_capacity, uint32_t tile_capacity,
+                         const float* image_state, void* scratch, size_t scratch_bytes, float* g_means3D, float* g_means2D,
+                         float* g_colors, float* g_colors_b, float* g_opacities, float* g_scales, float* g_rotations,
+                         void* stream, bool dual, const FrameEpilogue* frame = nullptr, bool cov3d = false) {
+  if (!cam_ok(cam) || n < 0 || !out_color || !grad_color || !workspace || !scratch || instance_capacity == 0 ||
+      instance_capacity > 0xFFFFFFFFull || (tile_capacity & ~VTGS_TILE_CAPACITY_PLANNED) == 0 || (dual && (!out_color_b || !grad_color_b)) || (frame && !dual))
+    return VTGS_ERR_INVALID_ARGUMENT;
+  const bool raw_act = frame && (frame->flags & 16u) != 0u;                // the forward's VTGS_FORWARD_RAW_ACTIVATIONS
+  if (raw_act && frame->idx) return VTGS_ERR_INVALID_ARGUMENT;             // (an owned list renders from fully prepared compact arrays)
+  if (n > 0 && (!means3D || !colors || !opacities || !scales || (!rotations && !cov3d && !raw_act) || (dual && !colors_b)))
+    return VTGS_ERR_INVALID_ARGUMENT;
+  if (cov3d && (dual || frame)) return VTGS_ERR_INVALID_ARGUMENT;
+  // any output may be NULL (a gradient nobody asked for -- the tracking loop detaches the Gaussians,
+  // src/vtgaussian_slam.py:428-449 -- is then neither stored nor its array allocated), but not all of them
+  if (n > 0 && !frame && !g_means3D && !g_means2D && !g_colors && !g_opacities && !g_scales && !g_rotations && !(dual && g_colors_b))
+    return VTGS_ERR_INVALID_ARGUMENT;
+  if (n > 0 && frame) {                                      // the gradients leave through the frame epilogue instead
+    const FrameEpilogue& f = *frame;
+    if (!f.means3D_world || !f.cam_q || !f.cam_t || !f.depth_w2c) return VTGS_ERR_INVALID_ARGUMENT;
+    if ((f.flags & 1u) && (!f.unnorm_rot || !f.g_means3D || !f.g_unnorm_rot)) return VTGS_ERR_INVALID_ARGUMENT;
+    if ((f.flags & 2u) && !f.pose_partials) return VTGS_ERR_INVALID_ARGUMENT;
+    if ((f.flags & 4u) && (!f.g_rgb || !f.g_logit || !f.g_log_scales)) return VTGS_ERR_INVALID_ARGUMENT;
+  }
+  int r8b, r8e, rows16, row16_0;
+  if (!band_of(cam, &r8b, &r8e, &rows16, &row16_0)) return VTGS_ERR_INVALID_ARGUMENT;
+  if (n == 0) return VTGS_OK;
+  const WsLayout L = make_layout(n, cam->image_width, cam->image_height, instance_capacity, tile_capacity);
+  if (workspace_bytes < L.total) return VTGS_ERR_WORKSPACE_TOO_SMALL;
+  if (scratch_bytes < (dual ? kGradRecDual : kGradRec) * sizeof(float)) return VTGS_ERR_INVALID_ARGUMENT;
+  hipStream_t st = (hipStream_t)stream;
+  const char* ws = (const char*)workspace;
+  CamScalars cs = scalars_of(cam, r8b, r8e);
+  if (L.planned) { cs.bin_plan = (const uint32_t*)(ws + L.plan); cs.bin_limit = L.tiles8 * L.tile_cap; }
+  const float* state = image_state ? image_state : (const float*)(ws + L.final_T);
+  const int gx16 = (cam->image_width + kBinTile - 1) / kBinTile;
+  const uint32_t nblk16 = (uint32_t)(gx16 * rows16);
+  uint32_t* dbg = option(OPT_COUNT_STEPS) == 1 ? (uint32_t*)(const_cast<char*>(ws) + L.dbg) : nullptr;   // measurement only
+  int bwd_impl = option(OPT_BWD_IMPL);                       // 2 = lane-per-pixel matrix-core replay (default), 1 = pixel x splat-quad replay,
+  // dL/d(first colour set) not asked for (tracking: the Gaussians are detached, src/vtgaussian_slam.py:428-449, and the pose
+  // gradient flows through means3D and the SECOND set's [z, 1, z^2] only): the lane = pixel backward skips that contraction chain
+  if (frame ? !(frame->flags & 4u) : !g_colors) cs.bwd_flags |= 1u;
+  cs.raw_act = raw_act ? 1u : 0u;
+  if (dual && bwd_impl == 0) bwd_impl = 1;                   // 0 = scalar kernel (single render only); read per call
+  if (dual && bwd_impl == 3) bwd_impl = 2;                   // 3 = quadrant queues (single render only so far)
+  // FrameEpilogue flag 8 (the caller's promise: grad_color_b is zero outside its first channel -- get_loss, whose loss reaches
+  // the [z, 1, z^2] render through z alone): four gradient channels instead of six, three contraction chains, 48-byte records
+  const bool b1 = dual && frame && (frame->flags & 8u) && bwd_impl == 2 && option(OPT_DUAL_B1) != 0;
+  {
+    const size_t rec_bytes = (size_t)(b1 ? kGradRecDual1 : (dual ? kGradRecDual : kGradRec)) * sizeof(float);
+    const size_t recs = scratch_bytes / rec_bytes;
+    cs.scratch_records = recs > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)recs;
+  }
+  {
+    ProfScope ps__(dual ? "composite_backward_dual" : "composite_backward", st);
+    if (bwd_impl == 2)                                      // lane = pixel replay (the default); b1 implies it
+      hipLaunchKernelGGL(backward_kernel(dual, b1), dim3(nblk16), dim3(256), 0, st, cs, cam->bg, nblk16,
+                         (const uint32_t*)(ws + L.tile_cnt), L.tile_cap, (const uint32_t*)(ws + L.sorted_gid),
+                         (const uint32_t*)(ws + L.sorted_inst), (const GeomRec*)(ws + L.geom), colors, out_color,
+                         grad_color, state, (float*)scratch, (const Counters*)(ws + L.counters), dual ? colors_b : nullptr,
+                         dual ? out_color_b : nullptr, dual ? grad_color_b : nullptr, dbg);
+    else {                                                  // quad form, scalar, quadrant queues: the test-only library
+      if (!xcheck_available()) return xcheck_missing();
+      const int rc = g_xcheck_backward(bwd_impl, dual ? 1 : 0, &cs, cam->bg, nblk16, (const uint32_t*)(ws + L.tile_cnt), L.tile_cap,
+                                       (const uint32_t*)(ws + L.sorted_gid), (const uint32_t*)(ws + L.sorted_inst),
+                                       (const uint8_t*)(ws + L.qmask), (const GeomRec*)(ws + L.geom), colors, out_color, grad_color,
+                                       state, (float*)scratch, (const Counters*)(ws + L.counters), colors_b, out_color_b,
+                                       grad_color_b, dbg, (void*)st);
+      if (rc != 0) return hip_fail(hipGetLastError(), "vtgs_xcheck_backward");
+    }
+  }
+  VTGS_HIP(hipGetLastError());
+  {
+    ProfScope ps__(dual ? "gather_splat_grads_dual" : "gather_splat_grads", st);
+    // what differs between the forms besides the kernel: the record layout's flag, where the gradients leave, the epilogue
+    const int moments_scaled_by_opacity = (dual || bwd_impl != 0) ? 1 : 0;
+    struct { float *means3D, *means2D, *colors, *opacities, *scales, *rotations, *colors_b; } g = {};   // (a frame epilogue carries them)
+    if (!frame) g = {g_means3D, g_means2D, g_colors, g_opacities, g_scales, cov3d ? nullptr : g_rotations, dual ? g_colors_b : nullptr};
+    hipLaunchKernelGGL(gather_kernel(dual, frame != nullptr, cov3d, b1), dim3((n + 255) / 256), dim3(256), 0, st, cs,
+                       cam->viewmatrix, cam->projmatrix, n, means3D, opacities, scales, rotations, (const GaussAux*)(ws + L.gaux),
+                       (const float*)scratch, moments_scaled_by_opacity, g.means3D, g.means2D, g.colors, g.opacities, g.scales,
+                       g.rotations, (const Counters*)(ws + L.counters), g.colors_b, frame ? *frame : FrameEpilogue{});
+  }
+  VTGS_HIP(hipGetLastError());
+  return VTGS_OK;
+}
+
+// fill + three histogram passes; the caller launches whatever finishes the select (lower_median_finish, or densify_count)
+int median_passes(const MedianSource& src, uint32_t n, MedianScratch* ms, hipStream_t st) {
+  {
+    ProfScope ps__("median_clear", st);
+    VTGS_HIP(hipMemsetAsync(ms, 0, kMedianClearBytes, st));
+  }
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + kMedianChunk - 1) / kMedianChunk, kMedianMaxGrid);
+  for (const auto& pass : kMedianPasses) {
+    ProfScope ps__(pass.profile_name, st);
+    hipLaunchKernelGGL(pass.kernel, dim3(grid), dim3(256), 0, st, src, n, ms);
+  }
+  VTGS_HIP(hipGetLastError());
+  return VTGS_OK;
+}
+
+// size checks and scratch carving of the densification, keyframe and tracking-mask entry points
+bool densify_sizes_ok(int32_t w, int32_t h, int32_t dw, int32_t dh) {
+  if (w <= 0 || h <= 0 || (int64_t)w * h > 0x7FFFFFFFll - kDensifyChunk) return false;
+  if (dw == 0) return true;
+  return dw > 0 && dh > 0 && (int64_t)dw * dh <= 0x7FFFFFFFll - kDensifyChunk && dw % w == 0 && dh % h == 0;
+}
+uint32_t densify_chunks(int32_t w, int32_t h) { return (uint32_t)(((int64_t)w * h + kDensifyChunk - 1) / kDensifyChunk); }
+
+bool keyframe_sizes_ok(int32_t w, int32_t h, int32_t samples, int32_t k) {
+  return w > 0 && h > 0 && (int64_t)w * h <= 0x7FFFFFFFll - 256 && samples >= 0 && samples <= 16384 && k > 0 && k <= (1 << 20);
+}
+size_t keyframe_bitmap_bytes(int32_t w, int32_t h) { return align256((((size_t)w * h + 31) / 32) * 4); }
+
+bool mask_sizes_ok(int32_t w, int32_t h, int32_t n, int32_t outlier) {
+  return w > 0 && h > 0 && (int64_t)w * h <= 0x7FFFFFFFll - 256 && n >= 0 && n <= 3 && (outlier == 0 || outlier == 1);
+}
+// scratch: [folded rows] [MedianScratch] [the median, one float] [err, H*W floats]; the last three only with the outlier mask
+size_t mask_rows_bytes(int32_t n) { return align256((size_t)n * sizeof(MaskRow)); }
+
+}  // namespace
+
+extern "C" {
+
+uint32_t vtgs_abi_version(void) { return VTGS_ABI_VERSION; }
+
+const char* vtgs_strerror(int status) {
+  switch (status) {
+    case VTGS_OK: return "ok";
+    case VTGS_ERR_INVALID_ARGUMENT: return "invalid argument";
+    case VTGS_ERR_WORKSPACE_TOO_SMALL: return "workspace too small";
+    case VTGS_ERR_INSTANCE_OVERFLOW: return "more (Gaussian,tile) instances than instance_capacity or a tile list longer than tile_capacity";
+    case VTGS_ERR_HIP: return "HIP runtime error";
+    case VTGS_ERR_STALE_WORKSPACE: return "workspace holds no completed forward for these sizes";
+    default: return "unknown status";
+  }
+}
+
+const char* vtgs_last_hip_error(void) { return g_hip_err; }
+
+size_t vtgs_workspace_bytes(int32_t n, int32_t width, int32_t height, uint64_t instance_capacity, uint32_t tile_capacity) {
+  if (n < 0 || width <= 0 || height <= 0 || (tile_capacity & ~VTGS_TILE_CAPACITY_PLANNED) == 0) return 0;
+  return make_layout(n, width, height, instance_capacity, tile_capacity).total;
+}
+
+size_t vtgs_workspace_clear_bytes(int32_t image_width, int32_t image_height) {
+  if (image_width <= 0 || image_height <= 0) return 0;
+  const size_t tiles8 = (size_t)((image_width + kSubTile - 1) / kSubTile) * (size_t)((image_height + kSubTile - 1) / kSubTile);
+  return 256 + align256((tiles8 + 1) * 4);       // WsLayout: counters at byte 0, tile_cnt behind them
+}
+
+size_t vtgs_backward_scratch_bytes(int32_t n, uint64_t instances) {
+  (void)n;
+  return align256((size_t)(instances ? instances : 1) * kGradRec * sizeof(float));
+}
+
+size_t vtgs_backward_dual_scratch_bytes(int32_t n, uint64_t instances) {
+  (void)n;
+  return align256((size_t)(instances ? instances : 1) * kGradRecDual * sizeof(float));
+}
+
+int vtgs_set_option(const char* name, int value) {
+  options_init();
+  if (!name) return VTGS_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < OPT_COUNT; ++i)
+    if (strcmp(name, g_options[i].name) == 0) { g_options[i].value = value < 0 ? g_options[i].dflt : value; return VTGS_OK; }
+  return VTGS_ERR_INVALID_ARGUMENT;
+}
+int vtgs_get_option(const char* name) {
+  options_init();
+  if (!name) return -1;
+  for (int i = 0; i < OPT_COUNT; ++i)
+    if (strcmp(name, g_options[i].name) == 0) return g_options[i].value;
+  return -1;
+}
+
 int vtgs_forward(const VtgsCamera* cam, int32_t n, const float* means3D, const float* colors, const float* opacities,
                  const float* scales, const float* rotations, float* out_color, float* out_depth, int32_t* out_radii,
                  void* workspace, size_t workspace_bytes, uint64_t instance_capacity, uint32_t tile_capacity,
@@ -582,124 +687,6 @@ int vtgs_forward_shared(const VtgsCamera* cam, int32_t n, const float* colors, f
     VTGS_HIP(hipMemsetAsync(out_depth, 0, P * sizeof(float), st));
   }
   return launch_composite_forward(cam, cs, rows16, L, (char*)workspace, colors, out_color, out_depth, image_state, st);
-}
-
-static int backward_impl(const VtgsCamera* cam, int32_t n, const float* means3D, const float* colors, const float* colors_b,
-                         const float* opacities, const float* scales, const float* rotations, const float* out_color,
-                         const float* out_color_b, const float* grad_color, const float* grad_color_b,
-                         const void* workspace, size_t workspace_bytes, uint64_t instance_capacity, uint32_t tile_capacity,
-                         const float* image_state, void* scratch, size_t scratch_bytes, float* g_means3D, float* g_means2D,
-                         float* g_colors, float* g_colors_b, float* g_opacities, float* g_scales, float* g_rotations,
-                         void* stream, bool dual, const FrameEpilogue* frame = nullptr, bool cov3d = false) {
-  if (!cam_ok(cam) || n < 0 || !out_color || !grad_color || !workspace || !scratch || instance_capacity == 0 ||
-      instance_capacity > 0xFFFFFFFFull || (tile_capacity & ~VTGS_TILE_CAPACITY_PLANNED) == 0 || (dual && (!out_color_b || !grad_color_b)) || (frame && !dual))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  const bool raw_act = frame && (frame->flags & 16u) != 0u;                // the forward's VTGS_FORWARD_RAW_ACTIVATIONS
-  if (raw_act && frame->idx) return VTGS_ERR_INVALID_ARGUMENT;             // (an owned list renders from fully prepared compact arrays)
-  if (n > 0 && (!means3D || !colors || !opacities || !scales || (!rotations && !cov3d && !raw_act) || (dual && !colors_b)))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  if (cov3d && (dual || frame)) return VTGS_ERR_INVALID_ARGUMENT;
-  // any output may be NULL (a gradient nobody asked for -- the tracking loop detaches the Gaussians,
-  // src/vtgaussian_slam.py:428-449 -- is then neither stored nor its array allocated), but not all of them
-  if (n > 0 && !frame && !g_means3D && !g_means2D && !g_colors && !g_opacities && !g_scales && !g_rotations && !(dual && g_colors_b))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  if (n > 0 && frame) {                                      // the gradients leave through the frame epilogue instead
-    const FrameEpilogue& f = *frame;
-    if (!f.means3D_world || !f.cam_q || !f.cam_t || !f.depth_w2c) return VTGS_ERR_INVALID_ARGUMENT;
-    if ((f.flags & 1u) && (!f.unnorm_rot || !f.g_means3D || !f.g_unnorm_rot)) return VTGS_ERR_INVALID_ARGUMENT;
-    if ((f.flags & 2u) && !f.pose_partials) return VTGS_ERR_INVALID_ARGUMENT;
-    if ((f.flags & 4u) && (!f.g_rgb || !f.g_logit || !f.g_log_scales)) return VTGS_ERR_INVALID_ARGUMENT;
-  }
-  int r8b, r8e, rows16, row16_0;
-  if (!band_of(cam, &r8b, &r8e, &rows16, &row16_0)) return VTGS_ERR_INVALID_ARGUMENT;
-  if (n == 0) return VTGS_OK;
-  const WsLayout L = make_layout(n, cam->image_width, cam->image_height, instance_capacity, tile_capacity);
-  if (workspace_bytes < L.total) return VTGS_ERR_WORKSPACE_TOO_SMALL;
-  if (scratch_bytes < (dual ? kGradRecDual : kGradRec) * sizeof(float)) return VTGS_ERR_INVALID_ARGUMENT;
-  hipStream_t st = (hipStream_t)stream;
-  const char* ws = (const char*)workspace;
-  CamScalars cs = scalars_of(cam, r8b, r8e);
-  if (L.planned) { cs.bin_plan = (const uint32_t*)(ws + L.plan); cs.bin_limit = L.tiles8 * L.tile_cap; }
-  const float* state = image_state ? image_state : (const float*)(ws + L.final_T);
-  const int gx16 = (cam->image_width + kBinTile - 1) / kBinTile;
-  const uint32_t nblk16 = (uint32_t)(gx16 * rows16);
-  uint32_t* dbg = option(OPT_COUNT_STEPS) == 1 ? (uint32_t*)(const_cast<char*>(ws) + L.dbg) : nullptr;   // measurement only
-  int bwd_impl = option(OPT_BWD_IMPL);                       // 2 = lane-per-pixel matrix-core replay (default), 1 = pixel x splat-quad replay,
-  // dL/d(first colour set) not asked for (tracking: the Gaussians are detached, src/vtgaussian_slam.py:428-449, and the pose
-  // gradient flows through means3D and the SECOND set's [z, 1, z^2] only): the lane = pixel backward skips that contraction chain
-  if (frame ? !(frame->flags & 4u) : !g_colors) cs.bwd_flags |= 1u;
-  cs.raw_act = raw_act ? 1u : 0u;
-  if (dual && bwd_impl == 0) bwd_impl = 1;                   // 0 = scalar kernel (single render only); read per call
-  if (dual && bwd_impl == 3) bwd_impl = 2;                   // 3 = quadrant queues (single render only so far)
-  // FrameEpilogue flag 8 (the caller's promise: grad_color_b is zero outside its first channel -- get_loss, whose loss reaches
-  // the [z, 1, z^2] render through z alone): four gradient channels instead of six, three contraction chains, 48-byte records
-  const bool b1 = dual && frame && (frame->flags & 8u) && bwd_impl == 2 && option(OPT_DUAL_B1) != 0;
-  {
-    const size_t rec_bytes = (size_t)(b1 ? kGradRecDual1 : (dual ? kGradRecDual : kGradRec)) * sizeof(float);
-    const size_t recs = scratch_bytes / rec_bytes;
-    cs.scratch_records = recs > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)recs;
-  }
-  {
-    ProfScope ps__(dual ? "composite_backward_dual" : "composite_backward", st);
-    if (b1)
-      hipLaunchKernelGGL((composite_backward_mx<4, true, true, true>), dim3(nblk16), dim3(256), 0, st, cs, cam->bg, nblk16,
-                         (const uint32_t*)(ws + L.tile_cnt), L.tile_cap, (const uint32_t*)(ws + L.sorted_gid),
-                         (const uint32_t*)(ws + L.sorted_inst), (const GeomRec*)(ws + L.geom), colors, out_color,
-                         grad_color, state, (float*)scratch, (const Counters*)(ws + L.counters), colors_b, out_color_b,
-                         grad_color_b, dbg);
-    else if (dual && bwd_impl == 2)
-      hipLaunchKernelGGL((composite_backward_mx<4, true, true, false>), dim3(nblk16), dim3(256), 0, st, cs, cam->bg, nblk16,
-                         (const uint32_t*)(ws + L.tile_cnt), L.tile_cap, (const uint32_t*)(ws + L.sorted_gid),
-                         (const uint32_t*)(ws + L.sorted_inst), (const GeomRec*)(ws + L.geom), colors, out_color,
-                         grad_color, state, (float*)scratch, (const Counters*)(ws + L.counters), colors_b, out_color_b,
-                         grad_color_b, dbg);
-    else if (!dual && bwd_impl == 2)                        // lane = pixel replay (the default)
-      hipLaunchKernelGGL((composite_backward_mx<4, false, true, false>), dim3(nblk16), dim3(256), 0, st, cs, cam->bg, nblk16,
-                         (const uint32_t*)(ws + L.tile_cnt), L.tile_cap, (const uint32_t*)(ws + L.sorted_gid),
-                         (const uint32_t*)(ws + L.sorted_inst), (const GeomRec*)(ws + L.geom), colors, out_color,
-                         grad_color, state, (float*)scratch, (const Counters*)(ws + L.counters), (const float*)nullptr,
-                         (const float*)nullptr, (const float*)nullptr, dbg);
-    else {                                                  // quad form, scalar, quadrant queues: the test-only library
-      if (!xcheck_available()) return xcheck_missing();
-      const int rc = g_xcheck_backward(bwd_impl, dual ? 1 : 0, &cs, cam->bg, nblk16, (const uint32_t*)(ws + L.tile_cnt), L.tile_cap,
-                                       (const uint32_t*)(ws + L.sorted_gid), (const uint32_t*)(ws + L.sorted_inst),
-                                       (const uint8_t*)(ws + L.qmask), (const GeomRec*)(ws + L.geom), colors, out_color, grad_color,
-                                       state, (float*)scratch, (const Counters*)(ws + L.counters), colors_b, out_color_b,
-                                       grad_color_b, dbg, (void*)st);
-      if (rc != 0) return hip_fail(hipGetLastError(), "vtgs_xcheck_backward");
-    }
-  }
-  VTGS_HIP(hipGetLastError());
-  {
-    ProfScope ps__(dual ? "gather_splat_grads_dual" : "gather_splat_grads", st);
-    if (b1)
-      hipLaunchKernelGGL((gather_splat_grads<true, true, false, true>), dim3((n + 255) / 256), dim3(256), 0, st, cs, cam->viewmatrix, cam->projmatrix, n,
-                         means3D, opacities, scales, rotations, (const GaussAux*)(ws + L.gaux), (const float*)scratch, 1,
-                         (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                         (const Counters*)(ws + L.counters), (float*)nullptr, *frame);
-    else if (dual && frame)
-      hipLaunchKernelGGL((gather_splat_grads<true, true, false, false>), dim3((n + 255) / 256), dim3(256), 0, st, cs, cam->viewmatrix, cam->projmatrix, n,
-                         means3D, opacities, scales, rotations, (const GaussAux*)(ws + L.gaux), (const float*)scratch, 1,
-                         (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                         (const Counters*)(ws + L.counters), (float*)nullptr, *frame);
-    else if (dual)
-      hipLaunchKernelGGL((gather_splat_grads<true, false, false, false>), dim3((n + 255) / 256), dim3(256), 0, st, cs, cam->viewmatrix, cam->projmatrix, n,
-                         means3D, opacities, scales, rotations, (const GaussAux*)(ws + L.gaux), (const float*)scratch, 1,
-                         g_means3D, g_means2D, g_colors, g_opacities, g_scales, g_rotations,
-                         (const Counters*)(ws + L.counters), g_colors_b, FrameEpilogue{});
-    else if (cov3d)
-      hipLaunchKernelGGL((gather_splat_grads<false, false, true, false>), dim3((n + 255) / 256), dim3(256), 0, st, cs, cam->viewmatrix, cam->projmatrix, n,
-                         means3D, opacities, scales, rotations, (const GaussAux*)(ws + L.gaux), (const float*)scratch, bwd_impl != 0 ? 1 : 0,
-                         g_means3D, g_means2D, g_colors, g_opacities, g_scales, (float*)nullptr,
-                         (const Counters*)(ws + L.counters), (float*)nullptr, FrameEpilogue{});
-    else
-      hipLaunchKernelGGL((gather_splat_grads<false, false, false, false>), dim3((n + 255) / 256), dim3(256), 0, st, cs, cam->viewmatrix, cam->projmatrix, n,
-                         means3D, opacities, scales, rotations, (const GaussAux*)(ws + L.gaux), (const float*)scratch, bwd_impl != 0 ? 1 : 0,
-                         g_means3D, g_means2D, g_colors, g_opacities, g_scales, g_rotations,
-                         (const Counters*)(ws + L.counters), (float*)nullptr, FrameEpilogue{});
-  }
-  VTGS_HIP(hipGetLastError());
-  return VTGS_OK;
 }
 
 int vtgs_backward(const VtgsCamera* cam, int32_t n, const float* means3D, const float* colors, const float* opacities,
@@ -797,29 +784,6 @@ int vtgs_band_owner_mask(const VtgsCamera* cam, int32_t n, const float* means3D,
 }
 
 // ---- exact lower median and densification (kernels: csrc/vtgs_densify.hip) -------------------------------------------------
-// fill + three histogram passes; the caller launches whatever finishes the select (lower_median_finish, or densify_count)
-static int median_passes(const MedianSource& src, uint32_t n, MedianScratch* ms, hipStream_t st) {
-  {
-    ProfScope ps__("median_clear", st);
-    VTGS_HIP(hipMemsetAsync(ms, 0, kMedianClearBytes, st));
-  }
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + kMedianChunk - 1) / kMedianChunk, kMedianMaxGrid);
-  {
-    ProfScope ps__("lower_median_pass0", st);
-    hipLaunchKernelGGL(lower_median_pass<0>, dim3(grid), dim3(256), 0, st, src, n, ms);
-  }
-  {
-    ProfScope ps__("lower_median_pass1", st);
-    hipLaunchKernelGGL(lower_median_pass<1>, dim3(grid), dim3(256), 0, st, src, n, ms);
-  }
-  {
-    ProfScope ps__("lower_median_pass2", st);
-    hipLaunchKernelGGL(lower_median_pass<2>, dim3(grid), dim3(256), 0, st, src, n, ms);
-  }
-  VTGS_HIP(hipGetLastError());
-  return VTGS_OK;
-}
-
 size_t vtgs_median_scratch_bytes(int64_t n) {
   if (n < 0 || n > 0xFFFFFFFFll) return 0;
   return align256(sizeof(MedianScratch));
@@ -842,13 +806,6 @@ int vtgs_lower_median(const float* values, int64_t n, void* scratch, size_t scra
   VTGS_HIP(hipGetLastError());
   return VTGS_OK;
 }
-
-static bool densify_sizes_ok(int32_t w, int32_t h, int32_t dw, int32_t dh) {
-  if (w <= 0 || h <= 0 || (int64_t)w * h > 0x7FFFFFFFll - kDensifyChunk) return false;
-  if (dw == 0) return true;
-  return dw > 0 && dh > 0 && (int64_t)dw * dh <= 0x7FFFFFFFll - kDensifyChunk && dw % w == 0 && dh % h == 0;
-}
-static uint32_t densify_chunks(int32_t w, int32_t h) { return (uint32_t)(((int64_t)w * h + kDensifyChunk - 1) / kDensifyChunk); }
 
 size_t vtgs_densify_scratch_bytes(int32_t width, int32_t height, int32_t dense_width, int32_t dense_height) {
   if (!densify_sizes_ok(width, height, dense_width, dense_height)) return 0;
@@ -918,11 +875,6 @@ int vtgs_densify(int32_t width, int32_t height, const float* depth_sil, const fl
 }
 
 // ---- keyframe overlap counts (kernels: csrc/vtgs_keyframes.hip) ----------------------------------------------------------------
-static bool keyframe_sizes_ok(int32_t w, int32_t h, int32_t samples, int32_t k) {
-  return w > 0 && h > 0 && (int64_t)w * h <= 0x7FFFFFFFll - 256 && samples >= 0 && samples <= 16384 && k > 0 && k <= (1 << 20);
-}
-static size_t keyframe_bitmap_bytes(int32_t w, int32_t h) { return align256((((size_t)w * h + 31) / 32) * 4); }
-
 size_t vtgs_keyframe_overlap_scratch_bytes(int32_t width, int32_t height, int32_t samples, int32_t k) {
   if (!keyframe_sizes_ok(width, height, samples, k)) return 0;
   return align256((size_t)k * sizeof(KeyframeRow)) + (samples ? 2 * keyframe_bitmap_bytes(width, height) : 0);
@@ -978,12 +930,6 @@ int vtgs_keyframe_overlap(int32_t width, int32_t height, const float* depth, con
 }
 
 // ---- tracking masks: visibility, far depth, outlier depth (kernels: csrc/vtgs_masks.hip) -----------------------------------------
-static bool mask_sizes_ok(int32_t w, int32_t h, int32_t n, int32_t outlier) {
-  return w > 0 && h > 0 && (int64_t)w * h <= 0x7FFFFFFFll - 256 && n >= 0 && n <= 3 && (outlier == 0 || outlier == 1);
-}
-// scratch: [folded rows] [MedianScratch] [the median, one float] [err, H*W floats]; the last three only with the outlier mask
-static size_t mask_rows_bytes(int32_t n) { return align256((size_t)n * sizeof(MaskRow)); }
-
 size_t vtgs_tracking_mask_scratch_bytes(int32_t width, int32_t height, int32_t n_overlaps, int32_t outlier) {
   if (!mask_sizes_ok(width, height, n_overlaps, outlier)) return 0;
   size_t b = mask_rows_bytes(n_overlaps);

@@ -7,6 +7,7 @@
 // and their autograd backward, including the N -> 12 reduction that carries dL/dmeans_cam back to the pose
 // (dL/dt = sum g, dL/dR = sum g p^T; the 12 -> 7 step through the quaternion is done by the caller on 12 floats).
 #include "../../include/vtgs.h"
+#include "vtgs_host.h"
 #include "vtgs_internal.h"
 #include "vtgs_kernels.h"
 
@@ -328,7 +329,7 @@ extern "C" {
 int vtgs_pose_slot_gather(const float* cam_unnorm_rots, const float* cam_trans, int32_t frames, int32_t t, float* pose7, void* stream) {
   if (!cam_unnorm_rots || !cam_trans || !pose7 || frames <= 0 || t < 0 || t >= frames) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(pose_slot_gather_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, cam_unnorm_rots, cam_trans, frames, t, pose7);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_pose_slot_scatter(const float* g_q, const float* g_t, int32_t frames, int32_t t, float* g_cam_unnorm_rots, float* g_cam_trans,
@@ -336,7 +337,7 @@ int vtgs_pose_slot_scatter(const float* g_q, const float* g_t, int32_t frames, i
   if (!g_cam_unnorm_rots || !g_cam_trans || frames <= 0 || t < 0 || t >= frames) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(pose_slot_scatter_kernel, dim3((7 * frames + 255) / 256), dim3(256), 0, (hipStream_t)stream, g_q, g_t, frames, t,
                      g_cam_unnorm_rots, g_cam_trans);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_pose_gradient(const float* pose_partials, uint32_t rows, const float* cam_q, float* g_cam_q, float* g_cam_t,
@@ -345,7 +346,7 @@ int vtgs_pose_gradient(const float* pose_partials, uint32_t rows, const float* c
   if ((uintptr_t)pose_partials & 15u) return VTGS_ERR_INVALID_ARGUMENT;                                  // (rows are read as three 16-byte words)
   hipLaunchKernelGGL(pose_gradient_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pose_partials, rows, cam_q, g_cam_q,
                      g_cam_t);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_pose_gradient_slot(const float* pose_partials, uint32_t rows, const float* cam_q, int32_t frames, int32_t t,
@@ -355,7 +356,7 @@ int vtgs_pose_gradient_slot(const float* pose_partials, uint32_t rows, const flo
   if ((uintptr_t)pose_partials & 15u) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(pose_gradient_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pose_partials, rows, cam_q, (float*)nullptr,
                      (float*)nullptr, (int)frames, (int)t, g_cam_unnorm_rots, g_cam_trans);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 uint32_t vtgs_pose_partial_rows(int32_t n) { return n > 0 ? (uint32_t)((n + 255) / 256) : 0u; }
@@ -370,7 +371,7 @@ int vtgs_prepare_frame_slot(int32_t n, const float* means3D, const float* logit_
   if ((clear_bytes && !clear) || ((uintptr_t)clear & 15u) || (clear_bytes & 15u) || clear_bytes > (1ull << 32))
     return VTGS_ERR_INVALID_ARGUMENT;
   if (n == 0) {                                                // an empty map: the pose still has to reach the caller's seven floats
-    if (clear_bytes && hipMemsetAsync(clear, 0, clear_bytes, (hipStream_t)stream) != hipSuccess) return VTGS_ERR_HIP;
+    if (clear_bytes) VTGS_HIP(hipMemsetAsync(clear, 0, clear_bytes, (hipStream_t)stream));
     return vtgs_pose_slot_gather(cam_unnorm_rots, cam_trans, frames, t, out_pose7, stream);
   }
   const bool lite = !out_opacities && !out_scales && !out_rotations;      // means_cam + depth colours only
@@ -381,14 +382,14 @@ int vtgs_prepare_frame_slot(int32_t n, const float* means3D, const float* logit_
     hipLaunchKernelGGL(prepare_frame_pose_kernel, dim3((n + 1023) / 1024), dim3(256), 0, (hipStream_t)stream, n, means3D,
                        cam_unnorm_rots + t, cam_trans + t, depth_w2c, out_means_cam, out_depth_colors, (int)frames, out_pose7,
                        (uint4*)clear, (uint32_t)(clear_bytes / 16));
-    return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+    return launch_status(__func__);
   }
-  if (clear_bytes && hipMemsetAsync(clear, 0, clear_bytes, (hipStream_t)stream) != hipSuccess) return VTGS_ERR_HIP;
+  if (clear_bytes) VTGS_HIP(hipMemsetAsync(clear, 0, clear_bytes, (hipStream_t)stream));
   hipLaunchKernelGGL(prepare_frame_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, (const int32_t*)nullptr,
                      means3D, logit_opacities, log_scales, unnorm_rotations, (const float*)nullptr, cam_unnorm_rots + t, cam_trans + t,
                      depth_w2c, out_means_cam, out_opacities, out_scales, out_rotations, out_depth_colors, (float*)nullptr,
                      (int)frames, out_pose7);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_prepare_frame(int32_t n, const float* means3D, const float* logit_opacities, const float* log_scales,
@@ -403,7 +404,7 @@ int vtgs_prepare_frame(int32_t n, const float* means3D, const float* logit_opaci
   hipLaunchKernelGGL(prepare_frame_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, (const int32_t*)nullptr,
                      means3D, logit_opacities, log_scales, unnorm_rotations, (const float*)nullptr, cam_q, cam_t, depth_w2c,
                      out_means_cam, out_opacities, out_scales, out_rotations, out_depth_colors, (float*)nullptr);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_prepare_frame_owned(int32_t n_owned, const int32_t* owned_idx, const float* means3D, const float* logit_opacities,
@@ -419,7 +420,7 @@ int vtgs_prepare_frame_owned(int32_t n_owned, const int32_t* owned_idx, const fl
   hipLaunchKernelGGL(prepare_frame_kernel, dim3((n_owned + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_owned, owned_idx,
                      means3D, logit_opacities, log_scales, unnorm_rotations, rgb_colors, cam_q, cam_t, depth_w2c,
                      out_means_cam, out_opacities, out_scales, out_rotations, out_depth_colors, out_rgb_colors);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_prepare_frame_backward(int32_t n, uint32_t flags, const float* means3D, const float* logit_opacities,
@@ -442,7 +443,7 @@ int vtgs_prepare_frame_backward(int32_t n, uint32_t flags, const float* means3D,
                      means3D, logit_opacities, log_scales, unnorm_rotations, cam_q, cam_t, depth_w2c, g_means_a, g_means_b,
                      g_depth_colors, g_opac_a, g_opac_b, g_scales_a, g_scales_b, g_rot_a, g_rot_b, g_means3D,
                      g_logit_opacities, g_log_scales, g_unnorm_rotations, pose_partials);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_pose7_reduce(int32_t n, const float* points, const float* g_points, float* partials, float* out7, void* stream) {
@@ -451,7 +452,7 @@ int vtgs_pose7_reduce(int32_t n, const float* points, const float* g_points, flo
   hipStream_t st = (hipStream_t)stream;
   if (rows) hipLaunchKernelGGL(pose7_partial_kernel, dim3(rows), dim3(256), 0, st, n, points, g_points, partials);
   hipLaunchKernelGGL(pose7_final_kernel, dim3(1), dim3(256), 0, st, partials, rows, out7);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 }  // extern "C"

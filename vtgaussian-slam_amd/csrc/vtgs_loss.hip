@@ -8,6 +8,7 @@
 //     A = d/dmu1 - 2 mu1 d/ds11 - mu2 d/ds12,  B = d/ds11,  C = d/ds12     (derivatives of the SSIM map)
 // and the backward is   dL/dx = g/(C H W) * ( blur(A) + 2 x blur(B) + y blur(C) )   -- three blurs, same tiling.
 #include "../../include/vtgs.h"
+#include "vtgs_host.h"
 #include "vtgs_internal.h"
 
 namespace vtgs {
@@ -619,7 +620,7 @@ int vtgs_masked_l1(const float* im, const float* depth_sil, const float* gt_im, 
     return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(masked_l1_kernel, dim3(vtgs_masked_l1_partial_rows(pixels)), dim3(256), 0, (hipStream_t)stream, im,
                      depth_sil, gt_im, gt_depth, pixels, sil_thres, mode, partial_sums, g_im, g_depth_sil);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_silhouette_sweep(const float* im, const float* silhouette, const float* gt_im, const float* gt_depth,
@@ -632,7 +633,7 @@ int vtgs_silhouette_sweep(const float* im, const float* silhouette, const float*
   for (int k = 0; k < 8; ++k) th.c[k] = k < n_thresholds ? thresholds[k] : 0.f;
   hipLaunchKernelGGL(silhouette_sweep_kernel, dim3(vtgs_masked_l1_partial_rows(pixels)), dim3(256), 0, (hipStream_t)stream,
                      im, silhouette, gt_im, gt_depth, pixels, th, partial_sums);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_adam_step(const VtgsAdamGroup* groups, int32_t n_groups, int32_t step, float beta1, float beta2, void* stream) {
@@ -658,7 +659,7 @@ int vtgs_adam_step(const VtgsAdamGroup* groups, int32_t n_groups, int32_t step, 
   a.beta2 = beta2;
   hipLaunchKernelGGL(adam_step_kernel, dim3((uint32_t)((longest + 1023) / 1024), (uint32_t)n_groups), dim3(256), 0,
                      (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_adam_step_rows(const VtgsAdamGroup* groups, int32_t n_groups, int32_t step, float beta1, float beta2,
@@ -691,7 +692,7 @@ int vtgs_adam_step_rows(const VtgsAdamGroup* groups, int32_t n_groups, int32_t s
   a.beta2 = beta2;
   hipLaunchKernelGGL(adam_step_rows_kernel, dim3((uint32_t)((longest + 255) / 256), (uint32_t)n_groups), dim3(256), 0,
                      (hipStream_t)stream, a, r);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 // seen_and_max_radius_block has no scalar fallback: radii / max_2d_radius are read as int4 / float4 and four `seen` bytes are
@@ -706,7 +707,7 @@ int vtgs_seen_and_max_radius(int32_t n, const int32_t* radii, float* max_2d_radi
   if (!bookkeeping_aligned(radii, max_2d_radius, seen)) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(seen_and_max_radius_kernel, dim3((uint32_t)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, n, radii,
                      max_2d_radius, seen);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 // workgroups of an SSIM launch over `tiles` tiles: what the chip holds at once (256 CUs x 3 workgroups of 41 KB LDS), every
@@ -729,7 +730,7 @@ int vtgs_ssim_forward(const float* img1, const float* img2, int32_t channels, in
   const int tx = (width + kST - 1) / kST, ty = (height + kST - 1) / kST;
   hipLaunchKernelGGL(ssim_forward_kernel, dim3(ssim_grid((uint32_t)(channels * tx * ty))), dim3(256), 0, (hipStream_t)stream, img1, img2, channels,
                      height, width, tx, ty, partial_sums, grad_maps);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_ssim_backward(const float* img1, const float* img2, const float* grad_maps, const float* upstream,
@@ -739,7 +740,7 @@ int vtgs_ssim_backward(const float* img1, const float* img2, const float* grad_m
   const int tx = (width + kST - 1) / kST, ty = (height + kST - 1) / kST;
   hipLaunchKernelGGL(ssim_backward_kernel, dim3(ssim_grid((uint32_t)(channels * tx * ty), 4u)), dim3(256), 0, (hipStream_t)stream, img1, img2, grad_maps,
                      upstream, channels, height, width, tx, ty, grad_img1, 1.f, 0.f);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 size_t vtgs_loss_scratch_floats(int32_t height, int32_t width) {
@@ -779,7 +780,7 @@ int vtgs_slam_loss_forward_seen(int32_t mode, const float* im, const float* dept
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1u + (uint32_t)((n + 1023) / 1024)), dim3(256), 0, st, scratch, l1_rows, ssim_partial,
                      ssim_rows, mode, w_im, w_depth, (float)((size_t)3 * P), out5, (mode == 1 && color_weight) ? 1.0f : 0.8f, 0,
                      (int)n, radii, max_2d_radius, seen);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_slam_loss_backward(int32_t mode, const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth,
@@ -799,7 +800,7 @@ int vtgs_slam_loss_backward(int32_t mode, const float* im, const float* depth_si
                        height, width, tx, ty, g_im, -0.2f * w_im, (color_weight ? 1.0f : 0.8f) * w_im / (float)((size_t)3 * P),
                        color_weight);
   }
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 // ---- one band of the tile-row partition: additive sums, the band's share, its gradient images -----------
@@ -830,7 +831,7 @@ int vtgs_slam_loss_band_sums(int32_t mode, const float* im, const float* depth_s
   }
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, l1_rows, ssim_partial, ssim_rows, mode, 0.f,
                      0.f, (float)((size_t)3 * P), sums8, 0.8f, 1);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_slam_loss_band_share(int32_t mode, const float* own_sums8, const float* all_sums8, int32_t height, int32_t width,
@@ -839,7 +840,7 @@ int vtgs_slam_loss_band_share(int32_t mode, const float* own_sums8, const float*
   if ((mode < 0 || mode > 2) || !own_sums8 || !all_sums8 || !out8 || height <= 0 || width <= 0) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(band_share_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, own_sums8, all_sums8, mode, w_im, w_depth,
                      (float)((size_t)3 * height * width), (mode == 1 && has_color_weight) ? 1.0f : 0.8f, first_band, out8);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_slam_loss_band_backward(int32_t mode, const float* im, const float* depth_sil, const float* gt_im,
@@ -861,7 +862,7 @@ int vtgs_slam_loss_band_backward(int32_t mode, const float* im, const float* dep
                        height, width, tx, ty, g_im, -0.2f * w_im, (color_weight ? 1.0f : 0.8f) * w_im / (float)((size_t)3 * P),
                        color_weight, ty0, row_begin, row_end);
   }
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_silhouette_sweep_band(const float* im, const float* silhouette, const float* gt_im, const float* gt_depth,
@@ -875,7 +876,7 @@ int vtgs_silhouette_sweep_band(const float* im, const float* silhouette, const f
   for (int k = 0; k < 8; ++k) th.c[k] = k < n_thresholds ? thresholds[k] : 0.f;
   hipLaunchKernelGGL(silhouette_sweep_kernel, dim3(vtgs_masked_l1_partial_rows(pixel_end - pixel_begin)), dim3(256), 0,
                      (hipStream_t)stream, im, silhouette, gt_im, gt_depth, pixels, th, partial_sums, pixel_begin, pixel_end);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 }  // extern "C"

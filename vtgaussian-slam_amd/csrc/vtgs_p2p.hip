@@ -13,6 +13,7 @@
 //                frame (derivation at window_radius below).  Writes n . (p_source - p_target) per matched pixel.
 // The reduction (sum of squares / max / mean of the 100 largest) is a torch reduction on the device in the Python layer.
 #include "../../include/vtgs.h"
+#include "vtgs_host.h"
 #include "vtgs_internal.h"
 
 namespace vtgs {
@@ -159,7 +160,7 @@ int vtgs_point2plane(int32_t width, int32_t height, const float* depth_target, c
                      w2c_target, w2c_source, frustum, tp, tn);
   hipLaunchKernelGGL(p2p_source, dim3((P + 255) / 256), dim3(256), 0, st, width, height, depth_source, mask_source, intrinsics,
                      w2c_target, w2c_source, frustum, threshold, (const float4*)tp, (const float4*)tn, out_dist, out_matched);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 }  // extern "C"

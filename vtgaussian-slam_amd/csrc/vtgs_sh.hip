@@ -10,6 +10,7 @@
 // autograd behind it): dir = (mean - campos) / |mean - campos|; colour = sum_k Y_k(dir) sh[k] + 0.5, real SH basis up to
 // degree 3 with the usual constants; negative channels are clamped to 0 and pass no gradient.
 #include "../../include/vtgs.h"
+#include "vtgs_host.h"
 #include "vtgs_internal.h"
 
 namespace vtgs {
@@ -124,7 +125,7 @@ int vtgs_sh_forward(int32_t n, int32_t degree, int32_t coeffs, const float* mean
   if (!means3D || !shs || !out_colors || !out_clamped) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(sh_forward_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, degree, coeffs, means3D, campos, shs,
                      out_colors, out_clamped);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 int vtgs_sh_backward(int32_t n, int32_t degree, int32_t coeffs, const float* means3D, const float* campos, const float* shs,
@@ -134,7 +135,7 @@ int vtgs_sh_backward(int32_t n, int32_t degree, int32_t coeffs, const float* mea
   if (!means3D || !shs || !clamped || !g_colors || (!g_shs && !g_means3D)) return VTGS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(sh_backward_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, degree, coeffs, means3D, campos,
                      shs, clamped, g_colors, g_shs, g_means3D);
-  return hipGetLastError() == hipSuccess ? VTGS_OK : VTGS_ERR_HIP;
+  return launch_status(__func__);
 }
 
 }  // extern "C"

@@ -10,53 +10,57 @@
 
 using namespace vtgs;
 
+namespace {
+
+// The templated composites, each instantiation named once.  Those of a row share a function type (csrc/vtgs_kernels.h; the
+// quad form and the lane = pixel forward have the same parameters), so one launch takes whichever pointer was chosen.
+using ForwardKernel = decltype(&composite_forward_mx<4, false>);
+using BackwardKernel = decltype(&composite_backward_mx<4, false, false, false>);
+const ForwardKernel kForwardKernels[2][2] = {            // [dual][lane = pixel]
+    {composite_forward_mx<4, false>, composite_forward_px<4, false>},
+    {composite_forward_mx<4, true>, composite_forward_px<4, true>}};
+const BackwardKernel kBackwardKernels[2] = {             // [dual]: the quad form
+    composite_backward_mx<4, false, false, false>, composite_backward_mx<4, true, false, false>};
+
+}  // namespace
+
 extern "C" {
 
 // must equal the number libvtgs.so was built with: the argument records (CamScalars, GeomRec, Counters) are shared headers
 uint32_t vtgs_xcheck_abi_version(void) { return VTGS_ABI_VERSION; }
 
-// impl: 0 scalar, 1 quad form, 2 lane = pixel.  dual != 0: colors_b / out_color_b valid, no depth image (impl 0 has no dual form).
+// impl: 0 scalar, 1 quad form, 2 lane = pixel.  dual != 0: colors_b / out_color_b valid, no depth image (impl 0 has no dual form:
+// a dual render takes the lane = pixel kernel unless the quad form is asked for).
 int vtgs_xcheck_forward(int impl, int dual, const CamScalars* cs, const float* bg, uint32_t nblk, const uint32_t* tile_cnt,
                         uint32_t tile_cap, const uint32_t* sorted_gid, const GeomRec* geom, const float* colors, float* out_color,
                         float* out_depth, float* final_T, const Counters* ctr, const float* colors_b, float* out_color_b,
                         void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (dual && impl != 1)
-    hipLaunchKernelGGL((composite_forward_px<4, true>), dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid,
-                       geom, colors, out_color, (float*)nullptr, final_T, ctr, colors_b, out_color_b);
-  else if (dual)
-    hipLaunchKernelGGL((composite_forward_mx<4, true>), dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid,
-                       geom, colors, out_color, (float*)nullptr, final_T, ctr, colors_b, out_color_b);
-  else if (impl == 2)
-    hipLaunchKernelGGL((composite_forward_px<4, false>), dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid,
-                       geom, colors, out_color, out_depth, final_T, ctr, (const float*)nullptr, (float*)nullptr);
-  else if (impl == 1)
-    hipLaunchKernelGGL((composite_forward_mx<4, false>), dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid,
-                       geom, colors, out_color, out_depth, final_T, ctr, (const float*)nullptr, (float*)nullptr);
+  const bool pxl = dual ? impl != 1 : impl == 2;
+  if (dual || impl == 1 || impl == 2)
+    hipLaunchKernelGGL(kForwardKernels[dual ? 1 : 0][pxl ? 1 : 0], dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap,
+                       sorted_gid, geom, colors, out_color, dual ? nullptr : out_depth, final_T, ctr, dual ? colors_b : nullptr,
+                       dual ? out_color_b : nullptr);
   else
     hipLaunchKernelGGL(composite_forward, dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid, geom, colors,
                        out_color, out_depth, final_T, ctr);
   return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 
-// impl: 0 scalar (single render), 1 quad form, 3 quadrant queues (single render).
+// impl: 0 scalar (single render), 1 quad form, 3 quadrant queues (single render).  A dual render always takes the quad form.
 int vtgs_xcheck_backward(int impl, int dual, const CamScalars* cs, const float* bg, uint32_t nblk, const uint32_t* tile_cnt,
                          uint32_t tile_cap, const uint32_t* sorted_gid, const uint32_t* sorted_inst, const uint8_t* qmask,
                          const GeomRec* geom, const float* colors, const float* out_color, const float* grad_color,
                          const float* state, float* grad_inst, const Counters* ctr, const float* colors_b,
                          const float* out_color_b, const float* grad_color_b, uint32_t* dbg, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (dual)
-    hipLaunchKernelGGL((composite_backward_mx<4, true, false, false>), dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap,
-                       sorted_gid, sorted_inst, geom, colors, out_color, grad_color, state, grad_inst, ctr, colors_b, out_color_b,
-                       grad_color_b, dbg);
+  if (dual || impl == 1)
+    hipLaunchKernelGGL(kBackwardKernels[dual ? 1 : 0], dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid,
+                       sorted_inst, geom, colors, out_color, grad_color, state, grad_inst, ctr, dual ? colors_b : nullptr,
+                       dual ? out_color_b : nullptr, dual ? grad_color_b : nullptr, dbg);
   else if (impl == 3)
     hipLaunchKernelGGL(composite_backward_q, dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid, sorted_inst,
                        qmask, geom, colors, out_color, grad_color, state, grad_inst, ctr, dbg);
-  else if (impl == 1)
-    hipLaunchKernelGGL((composite_backward_mx<4, false, false, false>), dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap,
-                       sorted_gid, sorted_inst, geom, colors, out_color, grad_color, state, grad_inst, ctr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, dbg);
   else
     hipLaunchKernelGGL(composite_backward, dim3(nblk), dim3(256), 0, st, *cs, bg, nblk, tile_cnt, tile_cap, sorted_gid, sorted_inst,
                        geom, colors, out_color, grad_color, state, grad_inst, ctr);
