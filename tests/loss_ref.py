@@ -1,4 +1,4 @@
-"""Float64 CPU statements of what csrc/vtgs_loss.hip computes, written from the text of include/vtgs.h -- TEST
+"""Float64 CPU statements of what csrc/vtgs_loss.hip and csrc/vtgs_adam.hip (Adam) compute, written from the text of include/vtgs.h -- TEST
 INFRASTRUCTURE, not part of the product -- and the hand-placed frames the path tests run them on.
 
 One function per operation (pixel terms, whole loss, SSIM map, silhouette sweep, one Adam step, the seen / max-radius

@@ -1,4 +1,4 @@
-"""vtgs_adam_step / vtgs_adam_step_rows (csrc/vtgs_loss.hip) on every path: the float4 form, its one-by-one tail, the form
+"""vtgs_adam_step / vtgs_adam_step_rows (csrc/vtgs_adam.hip) on every path: the float4 form, its one-by-one tail, the form
 taken when a base is not 16-byte aligned and the row-list kernel must give the same bits (the kernel's stated guarantee), a
 short group must survive sharing a launch with a long one, FusedAdam must chunk past VTGS_ADAM_MAX_GROUPS, and all of it must
 sit within a few float32 ulps of the float64 statement of the update in tests/loss_ref.py.  Every array lives between 64

@@ -10,9 +10,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_api.hip", "vtgs_binning.hip", "vtgs_composite_backward.hip", "vtgs_composite_q.hip",
-                                               "vtgs_densify.hip", "vtgs_frame.hip", "vtgs_gather.hip", "vtgs_keyframes.hip", "vtgs_loss.hip",
-                                               "vtgs_masks.hip", "vtgs_p2p.hip", "vtgs_sh.hip")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("vtgs_adam.hip", "vtgs_api.hip", "vtgs_binning.hip", "vtgs_composite_backward.hip",
+                                               "vtgs_composite_q.hip", "vtgs_densify.hip", "vtgs_frame.hip", "vtgs_gather.hip",
+                                               "vtgs_keyframes.hip", "vtgs_loss.hip", "vtgs_masks.hip", "vtgs_p2p.hip", "vtgs_sh.hip")]
 # the cross-check composites (scalar, quad form, lane = pixel forward, quadrant-queue backward): a TEST-ONLY library next to the
 # product, from sources of its own (only the header vtgs_composite_backward.h is shared); libvtgs.so opens it when an
 # implementation switch asks

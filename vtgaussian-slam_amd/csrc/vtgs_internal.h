@@ -264,6 +264,40 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 #endif
 }
 
+// ---------------------------------------------------------------- N floats at a time (loss and Adam kernels) ----
+// N consecutive floats of one array: N = 4 moves as one float4 (the address must be 16-byte aligned), N = 1 as one float.
+template <int N>
+struct Px {
+  static_assert(N == 1 || N == 4, "one float or one float4");
+  float v[N];
+  __device__ __forceinline__ float& operator[](int k) { return v[k]; }
+  __device__ __forceinline__ float operator[](int k) const { return v[k]; }
+  static __device__ __forceinline__ Px load(const float* p) {
+    Px r;
+    if constexpr (N == 4) { const float4 q = *reinterpret_cast<const float4*>(p); r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w; }
+    else r.v[0] = *p;
+    return r;
+  }
+  static __device__ __forceinline__ Px all(float x) {
+    Px r;
+#pragma unroll
+    for (int k = 0; k < N; ++k) r.v[k] = x;
+    return r;
+  }
+  // an optional array (a mask, a weight): null reads as all ones
+  static __device__ __forceinline__ Px load_or_ones(const float* base, size_t i) { return base ? load(base + i) : all(1.f); }
+  __device__ __forceinline__ void store(float* p) const {
+    if constexpr (N == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *p = v[0];
+  }
+};
+
+// whether every pointer that is not null is 16-byte aligned (null is address 0: it adds nothing to the OR)
+template <class... T>
+__host__ __device__ __forceinline__ bool all_aligned16(const T*... p) {
+  return ((... | reinterpret_cast<uintptr_t>(p)) & 15u) == 0u;
+}
+
 // XCD-aware block remap (8 XCDs, blocks dealt round-robin): gives each XCD a contiguous chunk of
 // the index space so neighbouring tiles share an L2.  Bijective for any nblk.
 __device__ __forceinline__ uint32_t xcd_swizzle(uint32_t bid, uint32_t nblk) {

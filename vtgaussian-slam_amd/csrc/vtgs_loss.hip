@@ -32,22 +32,56 @@ __device__ __forceinline__ void gauss11(float (&w)[11]) {
   for (int i = 0; i < 11; ++i) w[i] = k[i];
 }
 
+// ---- what the two SSIM kernels share: which tile, which staged pixels, the blur ------------------------------------------
+// tile b of a launch of C x tiles_y x tiles_x tiles whose first tile row is ty0
+struct SsimTile { int c, ty, tx; };
+__device__ __forceinline__ SsimTile ssim_tile(int b, int tiles_x, int tiles_y, int ty0) {
+  const int c = b / (tiles_x * tiles_y), tb = b - c * tiles_x * tiles_y;
+  return SsimTile{c, ty0 + tb / tiles_x, tb - (tb / tiles_x) * tiles_x};
+}
+
+// The thread's kStage positions in the staged patch of a tile: visit(k, gy, gx, in_patch) with the image row and column of
+// position t + 256 k (in_patch: that position exists -- the last slot of most threads does not).
+// (the staging was a third of the kernels' vector instructions: a division, 64-bit address arithmetic and a branch per
+//  pixel.  Now: the position advances by 256 = 6 x 42 + 4, offsets are 32-bit from a uniform plane pointer, and the caller
+//  loads a pixel it does not want from an offset that is always valid and replaces it by zero -- no branch)
+constexpr int kStage = (kSP * kSP + 255) / 256;                       // 7 staged pixels per thread and image
+template <class Visit>
+__device__ __forceinline__ void ssim_stage_walk(const SsimTile& tile, Visit&& visit) {
+  const int t = (int)threadIdx.x, x0 = tile.tx * kST - kSR, y0 = tile.ty * kST - kSR;
+  int r = t / kSP, q = t - r * kSP;                                   // patch position of the thread's first staged pixel
+#pragma unroll
+  for (int k = 0; k < kStage; ++k) {
+    visit(k, y0 + r, x0 + q, k < kStage - 1 || t + 256 * k < kSP * kSP);
+    q += 256 - 6 * kSP; r += 6;
+    if (q >= kSP) { q -= kSP; r += 1; }
+  }
+}
+
+// Output o of the 11-tap blur over a register window: both passes of both kernels slide the window in registers, a work item
+// produces FOUR adjacent outputs from 14 staged values instead of 4 x 11 (the kernels were bound by their LDS reads).  Every
+// output accumulates its taps in the order 0..10, so the values are the ones of the one-output-per-item form.  T = f32x2s
+// blurs a pair with one packed fma per tap.
+template <class T>
+__device__ __forceinline__ T blur11(const float (&w)[11], const T (&v)[14], int o) {
+  T s = (T)0.f;
+#pragma unroll
+  for (int k = 0; k < 11; ++k) s = __builtin_elementwise_fma((T)w[k], v[o + k], s);
+  return s;
+}
+
 __global__ __launch_bounds__(256) void ssim_forward_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
                                                            int C, int H, int W, int tiles_x, int tiles_y,
                                                            float* __restrict__ partial, float* __restrict__ gmaps,
-                                                           int ty0 = 0, int rb = 0, int re = 1 << 30) {
+                                                           int ty0, int rb, int re) {
   // band form (tile-row multi-GPU partition): tiles_y tile rows starting at ty0 are launched and only the SSIM pixels of
   // rows [rb, re) are summed / get derivative maps; the staged context rows around them are read as they are (the caller
-  // has put the neighbours' rows there).  Whole image: ty0 = 0, rb = 0, re >= H.
+  // has put the neighbours' rows there).  Whole image: ty0 = 0, rb = 0, re = H.
   // pairs that are blurred together sit together in LDS (one ds_read_b64 = one packed operand, no register shuffling)
   __shared__ float2 pxy[kSP * kSP];                                   // (img1, img2)
   __shared__ float2 hzm[kSP * kST], hzs[kSP * kST];                   // row-blurred (x, y), (x^2, y^2)
   __shared__ float hzc[kSP * kST];                                    // row-blurred x y
   __shared__ float red[4];
-#ifdef VTGS_AB_SSIM_PAD                                         // occupancy experiment
-  __shared__ float ab_pad[VTGS_AB_SSIM_PAD];
-  if (C < 0) { ab_pad[threadIdx.x] = 1.f; __syncthreads(); if (ab_pad[(threadIdx.x + 1) & 255] == 2.f) return; }
-#endif
   float w[11];
   gauss11(w);
   const int t = (int)threadIdx.x;
@@ -56,36 +90,23 @@ __global__ __launch_bounds__(256) void ssim_forward_kernel(const float* __restri
   // were ~3 -- the rest was the wait for its own 2 x 1764 pixels with three workgroups per CU to hide it behind.  Same arithmetic
   // per tile, same partial-sum slot per tile: bit-identical results.
   const int ntile = C * tiles_x * tiles_y;
-  constexpr int kStage = (kSP * kSP + 255) / 256;                     // 7 staged pixels per thread and image
   float ra[kStage], rd[kStage];
-  const int rt = t / kSP, qt = t - rt * kSP;                          // patch position of the thread's first staged pixel
-  // (the staging was a third of the kernel's vector instructions: a division, 64-bit address arithmetic and a branch per
-  //  pixel.  Now: the position advances by 256 = 6 x 42 + 4, offsets are 32-bit from a uniform plane pointer, and a pixel
-  //  outside the image is loaded from offset 0 and replaced by zero -- no branch)
   auto fetch = [&](int bb) {
-    const int c_ = bb / (tiles_x * tiles_y), tb_ = bb - c_ * tiles_x * tiles_y;
-    const int ty_ = ty0 + tb_ / tiles_x, tx_ = tb_ - (tb_ / tiles_x) * tiles_x;
-    const int x0 = tx_ * kST - kSR, y0 = ty_ * kST - kSR;
-    const float* __restrict__ p1 = img1 + (size_t)c_ * H * W;
-    const float* __restrict__ p2 = img2 + (size_t)c_ * H * W;
-    int r = rt, q = qt;
-#pragma unroll
-    for (int k = 0; k < kStage; ++k) {
-      const int gy = y0 + r, gx = x0 + q;
-      const bool in = (k < kStage - 1 || t + 256 * k < kSP * kSP) && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;   // zero padding
+    const SsimTile tile = ssim_tile(bb, tiles_x, tiles_y, ty0);
+    const float* __restrict__ p1 = img1 + (size_t)tile.c * H * W;
+    const float* __restrict__ p2 = img2 + (size_t)tile.c * H * W;
+    ssim_stage_walk(tile, [&](int k, int gy, int gx, bool in_patch) {
+      const bool in = in_patch && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;   // zero padding
       const int o = in ? gy * W + gx : 0;
       const float a1 = p1[o], a2 = p2[o];
       ra[k] = in ? a1 : 0.f;
       rd[k] = in ? a2 : 0.f;
-      q += 256 - 6 * kSP; r += 6;
-      if (q >= kSP) { q -= kSP; r += 1; }
-    }
+    });
   };
   if ((int)blockIdx.x < ntile) fetch((int)blockIdx.x);
   for (int b = (int)blockIdx.x; b < ntile; b += (int)gridDim.x) {
-  const int c = b / (tiles_x * tiles_y), tb = b - c * tiles_x * tiles_y;
-  const int ty = ty0 + tb / tiles_x, tx = tb - (tb / tiles_x) * tiles_x;
-  const size_t plane = (size_t)c * H * W;
+  const SsimTile tile = ssim_tile(b, tiles_x, tiles_y, ty0);
+  const size_t plane = (size_t)tile.c * H * W;
 #pragma unroll
   for (int k = 0; k < kStage; ++k) {
     const int i = t + 256 * k;
@@ -93,10 +114,7 @@ __global__ __launch_bounds__(256) void ssim_forward_kernel(const float* __restri
   }
   __syncthreads();
   if (b + (int)gridDim.x < ntile) fetch(b + (int)gridDim.x);          // in flight during both passes
-  // Both passes slide the window in registers: a work item produces FOUR adjacent outputs from 14 staged values instead of
-  // 4 x 11 (the kernel was bound by its LDS reads: 86 K per workgroup).  Every output still accumulates its 11 taps in the
-  // same order, so the values are the ones of the one-output-per-item form.
-  for (int i = t; i < kSP * (kST / 4); i += 256) {                    // rows: 42 x 32 outputs, 4 per item
+  for (int i = t; i < kSP * (kST / 4); i += 256) {                    // rows: 42 x 32 outputs, 4 per item (blur11)
     const int r = i / (kST / 4), q = 4 * (i - r * (kST / 4));
     f32x2s v[14], v2[14];
     float vxy[14];
@@ -107,17 +125,9 @@ __global__ __launch_bounds__(256) void ssim_forward_kernel(const float* __restri
     }
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      f32x2s m = {0.f, 0.f}, sq = {0.f, 0.f};
-      float xy = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const f32x2s wk = {w[k], w[k]};
-        m = __builtin_elementwise_fma(wk, v[o + k], m);
-        sq = __builtin_elementwise_fma(wk, v2[o + k], sq);
-        xy = fmaf(w[k], vxy[o + k], xy);
-      }
+      const f32x2s m = blur11(w, v, o), sq = blur11(w, v2, o);
       const int j = r * kST + q + o;
-      hzm[j] = make_float2(m.x, m.y); hzs[j] = make_float2(sq.x, sq.y); hzc[j] = xy;
+      hzm[j] = make_float2(m.x, m.y); hzs[j] = make_float2(sq.x, sq.y); hzc[j] = blur11(w, vxy, o);
     }
   }
   __syncthreads();
@@ -134,17 +144,9 @@ __global__ __launch_bounds__(256) void ssim_forward_kernel(const float* __restri
     }
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      const int r = r0 + o;
-      const int gy = ty * kST + r, gx = tx * kST + q;
-      f32x2s mm = {0.f, 0.f}, sq = {0.f, 0.f};
-      float xy = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const f32x2s wk = {w[k], w[k]};
-        mm = __builtin_elementwise_fma(wk, hm_[o + k], mm);
-        sq = __builtin_elementwise_fma(wk, hs_[o + k], sq);
-        xy = fmaf(w[k], hc_[o + k], xy);
-      }
+      const int gy = tile.ty * kST + r0 + o, gx = tile.tx * kST + q;
+      const f32x2s mm = blur11(w, hm_, o), sq = blur11(w, hs_, o);
+      const float xy = blur11(w, hc_, o);
       const float m1 = mm.x, m2 = mm.y, xx = sq.x, yy = sq.y;
       if (gy < H && gx < W && gy >= rb && gy < re) {
         const float s11 = xx - m1 * m1, s22 = yy - m2 * m2, s12 = xy - m1 * m2;
@@ -183,8 +185,7 @@ __global__ __launch_bounds__(256) void ssim_backward_kernel(const float* __restr
                                                             const float* __restrict__ gmaps, const float* __restrict__ upstream,
                                                             int C, int H, int W, int tiles_x, int tiles_y,
                                                             float* __restrict__ g_img1, float ssim_coef, float l1_coef,
-                                                            const float* __restrict__ l1_weight = nullptr,
-                                                            int ty0 = 0, int rb = 0, int re = 1 << 30) {
+                                                            const float* __restrict__ l1_weight, int ty0, int rb, int re) {
   // band form: the derivative maps exist on rows [rb, re) only (anything else counts as zero); the gradient is written on
   // rows [rb - 5, re + 5) -- the blur carries it into the neighbours' rows -- and the L1 term belongs to rows [rb, re).
   __shared__ float2 pm01[kSP * kSP];                                  // maps A, B as a pair (see the forward), C apart
@@ -196,36 +197,26 @@ __global__ __launch_bounds__(256) void ssim_backward_kernel(const float* __restr
   const int t = (int)threadIdx.x;
   const size_t P3 = (size_t)C * H * W;
   const int ntile = C * tiles_x * tiles_y;                            // tiles walked with the next one's patch in flight (see the forward)
-  constexpr int kStage = (kSP * kSP + 255) / 256;
   float rm[3][kStage];
-  const int rt = t / kSP, qt = t - rt * kSP;
   const int row_lo = rb > 0 ? rb : 0, row_hi = re < H ? re : H;       // the maps exist on these rows
-  auto fetch = [&](int bb) {                                          // (staging as in the forward: no division, no branch)
-    const int c_ = bb / (tiles_x * tiles_y), tb_ = bb - c_ * tiles_x * tiles_y;
-    const int ty_ = ty0 + tb_ / tiles_x, tx_ = tb_ - (tb_ / tiles_x) * tiles_x;
-    const int x0 = tx_ * kST - kSR, y0 = ty_ * kST - kSR;
-    const float* __restrict__ g0 = gmaps + (size_t)c_ * H * W;
+  auto fetch = [&](int bb) {
+    const SsimTile tile = ssim_tile(bb, tiles_x, tiles_y, ty0);
+    const float* __restrict__ g0 = gmaps + (size_t)tile.c * H * W;
     const float* __restrict__ g1 = g0 + P3;
     const float* __restrict__ g2 = g1 + P3;
-    int r = rt, q = qt;
-#pragma unroll
-    for (int k = 0; k < kStage; ++k) {
-      const int gy = y0 + r, gx = x0 + q;
-      const bool in = (k < kStage - 1 || t + 256 * k < kSP * kSP) && gy >= row_lo && gy < row_hi && (unsigned)gx < (unsigned)W;   // the adjoint of a zero-padded blur is the same blur
+    ssim_stage_walk(tile, [&](int k, int gy, int gx, bool in_patch) {
+      const bool in = in_patch && gy >= row_lo && gy < row_hi && (unsigned)gx < (unsigned)W;   // the adjoint of a zero-padded blur is the same blur
       const int o = in ? gy * W + gx : row_lo * W;
       const float a0 = g0[o], a1 = g1[o], a2 = g2[o];
       rm[0][k] = in ? a0 : 0.f; rm[1][k] = in ? a1 : 0.f; rm[2][k] = in ? a2 : 0.f;
-      q += 256 - 6 * kSP; r += 6;
-      if (q >= kSP) { q -= kSP; r += 1; }
-    }
+    });
   };
   if ((int)blockIdx.x < ntile) fetch((int)blockIdx.x);
   const float scale = upstream[0] * ssim_coef / (float)((size_t)C * H * W);
   const float l1s = upstream[0] * l1_coef;
   for (int b = (int)blockIdx.x; b < ntile; b += (int)gridDim.x) {
-  const int c = b / (tiles_x * tiles_y), tb = b - c * tiles_x * tiles_y;
-  const int ty = ty0 + tb / tiles_x, tx = tb - (tb / tiles_x) * tiles_x;
-  const size_t plane = (size_t)c * H * W;
+  const SsimTile tile = ssim_tile(b, tiles_x, tiles_y, ty0);
+  const size_t plane = (size_t)tile.c * H * W;
 #pragma unroll
   for (int k = 0; k < kStage; ++k) {
     const int i = t + 256 * k;
@@ -244,16 +235,9 @@ __global__ __launch_bounds__(256) void ssim_backward_kernel(const float* __restr
     }
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      f32x2s s01 = {0.f, 0.f};
-      float s2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const f32x2s wk = {w[k], w[k]};
-        s01 = __builtin_elementwise_fma(wk, v01[o + k], s01);
-        s2 = fmaf(w[k], v2_[o + k], s2);
-      }
+      const f32x2s s01 = blur11(w, v01, o);
       const int j = r * kST + q + o;
-      hz01[j] = make_float2(s01.x, s01.y); hz2[j] = s2;
+      hz01[j] = make_float2(s01.x, s01.y); hz2[j] = blur11(w, v2_, o);
     }
   }
   __syncthreads();
@@ -269,17 +253,10 @@ __global__ __launch_bounds__(256) void ssim_backward_kernel(const float* __restr
     }
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      const int gy = ty * kST + r0 + o, gx = tx * kST + q;
+      const int gy = tile.ty * kST + r0 + o, gx = tile.tx * kST + q;
       if (gy >= H || gx >= W || gy < rb - kSR || gy >= re + kSR) continue;
-      f32x2s s01 = {0.f, 0.f};
-      float s2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const f32x2s wk = {w[k], w[k]};
-        s01 = __builtin_elementwise_fma(wk, h01[o + k], s01);
-        s2 = fmaf(w[k], h2_[o + k], s2);
-      }
-      const float s0 = s01.x, s1 = s01.y;
+      const f32x2s s01 = blur11(w, h01, o);
+      const float s0 = s01.x, s1 = s01.y, s2 = blur11(w, h2_, o);
       // (the tile's own pixels are read here, not with the next tile's patch: eight more registers in flight across the
       //  blurs cost the fourth wavefront per SIMD, 26 -> 29 us)
       const int o2 = gy * W + gx;                                     // uniform bases, 32-bit offsets
@@ -299,85 +276,82 @@ __global__ __launch_bounds__(256) void ssim_backward_kernel(const float* __restr
 // mode 2 (tracking with neither use_sil_for_loss nor ignore_outlier_depth_loss, src/vtgaussian_slam.py:601-602): the depth
 //                    term as in mode 0, the colour SUM over all pixels
 // Gradient images hold d(sum)/d(im) and d(sum)/d(depth_sil[0]) (channels 1, 2 of depth_sil only enter detached masks).
+
+// ---- what masked_l1_kernel (the value) and loss_backward_kernel (the gradient) share, so that both mask the same pixels ----
+// the depth mask of one pixel; extra: the visibility / far-depth / outlier masks of the other datasets (1 when there is none)
+__device__ __forceinline__ bool depth_mask(int mode, float sil_thres, float depth, float sil, float depth_sq, float gt_depth, float extra) {
+  const float unc = depth_sq - depth * depth;
+  bool m = gt_depth > 0.f && depth == depth && unc == unc;
+  if (mode != 1) m = m && sil > sil_thres;
+  return m && extra != 0.f;
+}
+// the colour terms run over the depth mask in mode 0 and over all pixels in modes 1 and 2
+__device__ __forceinline__ bool colour_mask(int mode, bool m) { return mode == 0 ? m : true; }
+// c * d|e|/dx for e = target - x on the mask, else 0
+__device__ __forceinline__ float l1_grad(bool on, float e, float c) { return on ? (e > 0.f ? -c : (e < 0.f ? c : 0.f)) : 0.f; }
+// s + |e| w of the colour sum.  Left to the compiler, which of these multiply-adds are fused changes with the code around
+// them, and the partial sums with it; so contraction is off and the rounding is spelled out as both forms of the kernel have
+// always had it: a pixel's first channel rounds its product before the addition, its other two are fused.
+__device__ __forceinline__ float add_weighted_abs(float s, float e, float w, bool fused) {
+#pragma clang fp contract(off)
+  return fused ? fmaf(fabsf(e), w, s) : s + fabsf(e) * w;
+}
+
+// The pixels [p0, p1) of planes of stride P over a grid of 256-thread workgroups: body(PxCount<4>, i) for the groups of four
+// in [p0, pv) when `aligned` (every base 16-byte aligned) and P and p0 are multiples of 4, then body(PxCount<1>, i) for
+// [pv, p1) one by one.  A thread's sums take its fours first; the body runs the lanes of a four in order.
+// (Round 5: a thread of the one-pixel form walked ~3 pixels one after the other with ten scalar loads each -- 12 us for 33 MB;
+//  every reference frame size takes the float4 form)
+template <int N> struct PxCount { static constexpr int value = N; };
+template <class Body>
+__device__ __forceinline__ void walk_pixels(int P, int p0, int p1, bool aligned, Body&& body) {
+  const bool vec = (P & 3) == 0 && (p0 & 3) == 0 && aligned;
+  const int pv = vec ? p0 + ((p1 - p0) & ~3) : p0;
+  for (int i = p0 + 4 * (int)(blockIdx.x * 256u + threadIdx.x); i < pv; i += 4 * (int)(gridDim.x * 256u)) body(PxCount<4>{}, i);
+  for (int i = pv + (int)(blockIdx.x * 256u + threadIdx.x); i < p1; i += (int)(gridDim.x * 256u)) body(PxCount<1>{}, i);
+}
+
 __global__ __launch_bounds__(256) void masked_l1_kernel(const float* __restrict__ im, const float* __restrict__ ds,
                                                         const float* __restrict__ gt_im, const float* __restrict__ gt_depth,
                                                         int P, float sil_thres, int mode, float* __restrict__ partial,
                                                         float* __restrict__ g_im, float* __restrict__ g_ds,
-                                                        const float* __restrict__ extra_mask = nullptr,
-                                                        const float* __restrict__ color_weight = nullptr,
-                                                        int p0 = 0, int p1 = -1) {
+                                                        const float* __restrict__ extra_mask,
+                                                        const float* __restrict__ color_weight, int p0, int p1) {
   // [p0, p1): the pixels this call sums (a band of rows of the tile-row partition); P stays the plane stride
   __shared__ float red[4][3];
   float s_im = 0.f, s_d = 0.f, cnt = 0.f;
-  if (p1 < 0) p1 = P;
-  // one pixel: the masks, the three sums, and (optionally) the unscaled gradient images
-  auto pixel = [&](float depth, float sil, float dsq, float gd, float em, const float (&x)[3], const float (&y)[3],
-                   const float (&cwv)[3], float& gds, float (&gim)[3]) {
-    const float unc = dsq - depth * depth;
-    bool m = gd > 0.f && depth == depth && unc == unc;
-    if (mode != 1) m = m && sil > sil_thres;
-    m = m && em != 0.f;                                      // visibility / far-depth / outlier masks of the other datasets
-    const bool mc = (mode == 0) ? m : true;
-    const float d = gd - depth;
-    s_d += m ? fabsf(d) : 0.f;
-    cnt += m ? 1.f : 0.f;
-    gds = m ? (d > 0.f ? -1.f : (d < 0.f ? 1.f : 0.f)) : 0.f;
+  // N pixels: the masks, the three sums, and (optionally) the unscaled gradient images
+  walk_pixels(P, p0, p1, all_aligned16(im, ds, gt_im, gt_depth, extra_mask, color_weight, g_im, g_ds), [&](auto n, int i) {
+    using V = Px<decltype(n)::value>;
+    const V depth = V::load(ds + i), sil = V::load(ds + P + i), dsq = V::load(ds + 2 * (size_t)P + i), gd = V::load(gt_depth + i);
+    const V em = V::load_or_ones(extra_mask, i);
+    V x[3], y[3], cw[3], gds, gim[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float e = y[c] - x[c];
-      s_im += mc ? fabsf(e) * cwv[c] : 0.f;                  // cw -- mapping: 10 additional_mask + 0.8
-      gim[c] = mc ? (e > 0.f ? -cwv[c] : (e < 0.f ? cwv[c] : 0.f)) : 0.f;
+      x[c] = V::load(im + (size_t)c * P + i);
+      y[c] = V::load(gt_im + (size_t)c * P + i);
+      cw[c] = V::load_or_ones(color_weight, (size_t)c * P + i);     // mapping: 10 additional_mask + 0.8
     }
-  };
-  // Round 5: FOUR pixels per thread as float4 when the planes allow it (plane stride and band start multiples of 4, 16-byte
-  // bases: every reference frame size): a thread of the one-pixel form walked ~3 pixels one after the other with ten scalar
-  // loads each -- 12 us for 33 MB.
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0u; };
-  const bool vec = (P & 3) == 0 && (p0 & 3) == 0 && al16(im) && al16(ds) && al16(gt_im) && al16(gt_depth) &&
-                   (!extra_mask || al16(extra_mask)) && (!color_weight || al16(color_weight)) && (!g_im || al16(g_im)) &&
-                   (!g_ds || al16(g_ds));
-  const int pv = vec ? p0 + ((p1 - p0) & ~3) : p0;           // [p0, pv) in groups of four, [pv, p1) one by one
-  for (int i = p0 + 4 * (int)(blockIdx.x * 256u + threadIdx.x); i < pv; i += 4 * (int)(gridDim.x * 256u)) {
-    const float4 dz = *reinterpret_cast<const float4*>(ds + i), sl = *reinterpret_cast<const float4*>(ds + P + i),
-                 dq = *reinterpret_cast<const float4*>(ds + 2 * (size_t)P + i), gd = *reinterpret_cast<const float4*>(gt_depth + i);
-    const float4 em = extra_mask ? *reinterpret_cast<const float4*>(extra_mask + i) : make_float4(1.f, 1.f, 1.f, 1.f);
-    float4 xs[3], ys[3], cws[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      xs[c] = *reinterpret_cast<const float4*>(im + (size_t)c * P + i);
-      ys[c] = *reinterpret_cast<const float4*>(gt_im + (size_t)c * P + i);
-      cws[c] = color_weight ? *reinterpret_cast<const float4*>(color_weight + (size_t)c * P + i) : make_float4(1.f, 1.f, 1.f, 1.f);
+    for (int k = 0; k < decltype(n)::value; ++k) {
+      const bool m = depth_mask(mode, sil_thres, depth[k], sil[k], dsq[k], gd[k], em[k]), mc = colour_mask(mode, m);
+      const float d = gd[k] - depth[k];
+      s_d += m ? fabsf(d) : 0.f;
+      cnt += m ? 1.f : 0.f;
+      gds[k] = l1_grad(m, d, 1.f);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float e = y[c][k] - x[c][k];
+        s_im = mc ? add_weighted_abs(s_im, e, cw[c][k], c > 0) : s_im;
+        gim[c][k] = l1_grad(mc, e, cw[c][k]);
+      }
     }
-    float gd4[4], gi4[3][4];
-#define VTGS_L1_PIXEL(k, F)                                                                              \
-    {                                                                                                     \
-      const float x[3] = {xs[0].F, xs[1].F, xs[2].F}, y[3] = {ys[0].F, ys[1].F, ys[2].F}, cwv[3] = {cws[0].F, cws[1].F, cws[2].F}; \
-      float gim[3];                                                                                       \
-      pixel(dz.F, sl.F, dq.F, gd.F, em.F, x, y, cwv, gd4[k], gim);                                        \
-      gi4[0][k] = gim[0]; gi4[1][k] = gim[1]; gi4[2][k] = gim[2];                                         \
-    }
-    VTGS_L1_PIXEL(0, x) VTGS_L1_PIXEL(1, y) VTGS_L1_PIXEL(2, z) VTGS_L1_PIXEL(3, w)
-#undef VTGS_L1_PIXEL
-    if (g_ds) {
-      *reinterpret_cast<float4*>(g_ds + i) = make_float4(gd4[0], gd4[1], gd4[2], gd4[3]);
-      *reinterpret_cast<float4*>(g_ds + P + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(g_ds + 2 * (size_t)P + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    if (g_ds) { gds.store(g_ds + i); V::all(0.f).store(g_ds + P + i); V::all(0.f).store(g_ds + 2 * (size_t)P + i); }
     if (g_im) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(g_im + (size_t)c * P + i) = make_float4(gi4[c][0], gi4[c][1], gi4[c][2], gi4[c][3]);
+      for (int c = 0; c < 3; ++c) gim[c].store(g_im + (size_t)c * P + i);
     }
-  }
-  for (int i = pv + (int)(blockIdx.x * 256u + threadIdx.x); i < p1; i += (int)(gridDim.x * 256u)) {
-    const float x[3] = {im[i], im[(size_t)P + i], im[2 * (size_t)P + i]};
-    const float y[3] = {gt_im[i], gt_im[(size_t)P + i], gt_im[2 * (size_t)P + i]};
-    const float cwv[3] = {color_weight ? color_weight[i] : 1.f, color_weight ? color_weight[(size_t)P + i] : 1.f,
-                          color_weight ? color_weight[2 * (size_t)P + i] : 1.f};
-    float gds, gim[3];
-    pixel(ds[i], ds[P + i], ds[2 * (size_t)P + i], gt_depth[i], extra_mask ? extra_mask[i] : 1.f, x, y, cwv, gds, gim);
-    if (g_ds) { g_ds[i] = gds; g_ds[P + i] = 0.f; g_ds[2 * (size_t)P + i] = 0.f; }
-    if (g_im) { g_im[i] = gim[0]; g_im[(size_t)P + i] = gim[1]; g_im[2 * (size_t)P + i] = gim[2]; }
-  }
+  });
   s_im = wave_sum(s_im); s_d = wave_sum(s_d); cnt = wave_sum(cnt);
   if (lane_id() == 0) { red[threadIdx.x >> 6][0] = s_im; red[threadIdx.x >> 6][1] = s_d; red[threadIdx.x >> 6][2] = cnt; }
   __syncthreads();
@@ -391,12 +365,11 @@ struct SweepThresholds { float c[8]; int n; };
 __global__ __launch_bounds__(256) void silhouette_sweep_kernel(const float* __restrict__ im, const float* __restrict__ sil,
                                                                const float* __restrict__ gt_im, const float* __restrict__ gt_depth,
                                                                int P, SweepThresholds th, float* __restrict__ partial,
-                                                               int p0 = 0, int p1 = -1) {
+                                                               int p0, int p1) {
   __shared__ float red[4][16];
   float sum[8], cnt[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { sum[k] = 0.f; cnt[k] = 0.f; }
-  if (p1 < 0) p1 = P;
   for (int i = p0 + (int)(blockIdx.x * 256u + threadIdx.x); i < p1; i += (int)(gridDim.x * 256u)) {
     const float e0 = gt_im[i] - im[i], e1 = gt_im[(size_t)P + i] - im[(size_t)P + i],
                 e2 = gt_im[2 * (size_t)P + i] - im[2 * (size_t)P + i];
@@ -418,61 +391,6 @@ __global__ __launch_bounds__(256) void silhouette_sweep_kernel(const float* __re
   __syncthreads();
   if ((int)threadIdx.x < 2 * th.n)
     partial[(size_t)blockIdx.x * 2 * th.n + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// ---- Adam over up to 8 tensors in one launch (src/vtgaussian_slam.py:180-187) ----------------------------------------------
-struct AdamLaunch {
-  VtgsAdamGroup g[VTGS_ADAM_MAX_GROUPS];
-  float step_size_scale;   // 1 / (1 - b1^step)
-  float sqrt_bias2;        // sqrt(1 - b2^step)
-  float beta1, beta2;
-};
-
-// one element of the update; the multiply-adds are spelled out (and contraction is off) so that the float4 form, the scalar
-// tail and the row-list kernel produce the same bits whatever the compiler would fuse in each of them
-__device__ __forceinline__ void adam_element(const AdamLaunch& a, const VtgsAdamGroup& g, float gr, float& m, float& v, float& p) {
-#pragma clang fp contract(off)
-  m = fmaf(1.f - a.beta1, gr - m, m);                                 // lerp, like torch
-  v = fmaf(a.beta2, v, ((1.f - a.beta2) * gr) * gr);
-  const float denom = sqrtf(v) / a.sqrt_bias2 + g.eps;
-  p = fmaf(-(g.lr * a.step_size_scale), m / denom, p);
-}
-// four elements per thread as float4 when the group's four arrays are 16-byte aligned (every torch allocation and the
-// padded segments of the fused nodes' gradient blocks are): the one-float form ran at ~3 TB/s (27 us for the five trainable
-// floats of 1 M Gaussians); same arithmetic per element
-__global__ __launch_bounds__(256) void adam_step_kernel(AdamLaunch a) {
-  const VtgsAdamGroup& g = a.g[blockIdx.y];
-  const size_t i = ((size_t)blockIdx.x * 256u + threadIdx.x) * 4u;
-  if (i >= g.count) return;
-  const bool vec = ((reinterpret_cast<uintptr_t>(g.param) | reinterpret_cast<uintptr_t>(g.grad) | reinterpret_cast<uintptr_t>(g.exp_avg) |
-                     reinterpret_cast<uintptr_t>(g.exp_avg_sq)) & 15u) == 0u;
-  if (vec && i + 4u <= g.count) {
-    const float4 gr = *reinterpret_cast<const float4*>(g.grad + i);
-    float4 m = *reinterpret_cast<const float4*>(g.exp_avg + i), v = *reinterpret_cast<const float4*>(g.exp_avg_sq + i);
-    float4 p = *reinterpret_cast<const float4*>(g.param + i);
-    adam_element(a, g, gr.x, m.x, v.x, p.x); adam_element(a, g, gr.y, m.y, v.y, p.y);
-    adam_element(a, g, gr.z, m.z, v.z, p.z); adam_element(a, g, gr.w, m.w, v.w, p.w);
-    *reinterpret_cast<float4*>(g.exp_avg + i) = m; *reinterpret_cast<float4*>(g.exp_avg_sq + i) = v;
-    *reinterpret_cast<float4*>(g.param + i) = p;
-    return;
-  }
-  for (size_t j = i; j < g.count && j < i + 4u; ++j) {
-    float m = g.exp_avg[j], v = g.exp_avg_sq[j], p = g.param[j];
-    adam_element(a, g, g.grad[j], m, v, p);
-    g.exp_avg[j] = m; g.exp_avg_sq[j] = v; g.param[j] = p;
-  }
-}
-
-struct AdamRows { const int32_t* rows; int32_t n_rows; uint32_t width[VTGS_ADAM_MAX_GROUPS]; };
-__global__ __launch_bounds__(256) void adam_step_rows_kernel(AdamLaunch a, AdamRows r) {
-  const VtgsAdamGroup& g = a.g[blockIdx.y];
-  const uint32_t w = r.width[blockIdx.y];
-  const size_t j = (size_t)blockIdx.x * 256u + threadIdx.x;
-  if (w == 0u || j >= (size_t)r.n_rows * w) return;
-  const size_t i = (size_t)r.rows[j / w] * w + (j % w);
-  float m = g.exp_avg[i], v = g.exp_avg_sq[i], p = g.param[i];
-  adam_element(a, g, g.grad[i], m, v, p);
-  g.exp_avg[i] = m; g.exp_avg_sq[i] = v; g.param[i] = p;
 }
 
 // seen = radius > 0 and the running maximum of the screen-space radius (src/vtgaussian_slam.py:681-689): four Gaussians per thread
@@ -540,54 +458,34 @@ __global__ __launch_bounds__(256) void loss_backward_kernel(const float* __restr
                                                             int P, float sil_thres, int mode, float w_im, float w_depth,
                                                             const float* __restrict__ upstream, const float* __restrict__ fwd_out,
                                                             float* __restrict__ g_im, float* __restrict__ g_ds,
-                                                            const float* __restrict__ extra_mask = nullptr,
-                                                            int p0 = 0, int p1 = -1) {
-  if (p1 < 0) p1 = P;
+                                                            const float* __restrict__ extra_mask, int p0, int p1) {
   const float up = upstream[0];
   const float cd = (mode != 1) ? up * w_depth : up * w_depth / fwd_out[1];
   const float ci = up * w_im;
-  auto mask_of = [&](float depth, float sil, float dsq, float gd, float em) {
-    const float unc = dsq - depth * depth;
-    bool m = gd > 0.f && depth == depth && unc == unc;
-    if (mode != 1) m = m && sil > sil_thres;
-    return m && em != 0.f;
-  };
-  auto gdepth = [&](bool m, float gd, float depth) { const float d = gd - depth; return m ? (d > 0.f ? -cd : (d < 0.f ? cd : 0.f)) : 0.f; };
-  auto gcol = [&](bool mc, float y, float x) { const float e = y - x; return mc ? (e > 0.f ? -ci : (e < 0.f ? ci : 0.f)) : 0.f; };
-  // four pixels per thread as float4 when the planes allow it (see masked_l1_kernel)
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0u; };
-  const bool vec = (P & 3) == 0 && (p0 & 3) == 0 && al16(ds) && al16(gt_depth) && al16(g_ds) && (!extra_mask || al16(extra_mask)) &&
-                   (mode == 1 || (al16(im) && al16(gt_im) && al16(g_im)));
-  const int pv = vec ? p0 + ((p1 - p0) & ~3) : p0;
-  for (int i = p0 + 4 * (int)(blockIdx.x * 256u + threadIdx.x); i < pv; i += 4 * (int)(gridDim.x * 256u)) {
-    const float4 dz = *reinterpret_cast<const float4*>(ds + i), sl = *reinterpret_cast<const float4*>(ds + P + i),
-                 dq = *reinterpret_cast<const float4*>(ds + 2 * (size_t)P + i), gd = *reinterpret_cast<const float4*>(gt_depth + i);
-    const float4 em = extra_mask ? *reinterpret_cast<const float4*>(extra_mask + i) : make_float4(1.f, 1.f, 1.f, 1.f);
-    const bool m0 = mask_of(dz.x, sl.x, dq.x, gd.x, em.x), m1 = mask_of(dz.y, sl.y, dq.y, gd.y, em.y),
-               m2 = mask_of(dz.z, sl.z, dq.z, gd.z, em.z), m3 = mask_of(dz.w, sl.w, dq.w, gd.w, em.w);
-    *reinterpret_cast<float4*>(g_ds + i) = make_float4(gdepth(m0, gd.x, dz.x), gdepth(m1, gd.y, dz.y), gdepth(m2, gd.z, dz.z), gdepth(m3, gd.w, dz.w));
-    *reinterpret_cast<float4*>(g_ds + P + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    *reinterpret_cast<float4*>(g_ds + 2 * (size_t)P + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+  const bool aligned = all_aligned16(ds, gt_depth, g_ds, extra_mask) && (mode == 1 || all_aligned16(im, gt_im, g_im));
+  walk_pixels(P, p0, p1, aligned, [&](auto n, int i) {
+    constexpr int N = decltype(n)::value;
+    using V = Px<N>;
+    const V depth = V::load(ds + i), sil = V::load(ds + P + i), dsq = V::load(ds + 2 * (size_t)P + i), gd = V::load(gt_depth + i);
+    const V em = V::load_or_ones(extra_mask, i);
+    bool m[N];
+    V g;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      m[k] = depth_mask(mode, sil_thres, depth[k], sil[k], dsq[k], gd[k], em[k]);
+      g[k] = l1_grad(m[k], gd[k] - depth[k], cd);
+    }
+    g.store(g_ds + i); V::all(0.f).store(g_ds + P + i); V::all(0.f).store(g_ds + 2 * (size_t)P + i);
     if (mode != 1) {
-      const bool c0 = mode == 0 ? m0 : true, c1 = mode == 0 ? m1 : true, c2 = mode == 0 ? m2 : true, c3 = mode == 0 ? m3 : true;   // mode 2: all pixels
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float4 x = *reinterpret_cast<const float4*>(im + (size_t)c * P + i), y = *reinterpret_cast<const float4*>(gt_im + (size_t)c * P + i);
-        *reinterpret_cast<float4*>(g_im + (size_t)c * P + i) = make_float4(gcol(c0, y.x, x.x), gcol(c1, y.y, x.y), gcol(c2, y.z, x.z), gcol(c3, y.w, x.w));
+        const V x = V::load(im + (size_t)c * P + i), y = V::load(gt_im + (size_t)c * P + i);
+#pragma unroll
+        for (int k = 0; k < N; ++k) g[k] = l1_grad(colour_mask(mode, m[k]), y[k] - x[k], ci);
+        g.store(g_im + (size_t)c * P + i);
       }
     }
-  }
-  for (int i = pv + (int)(blockIdx.x * 256u + threadIdx.x); i < p1; i += (int)(gridDim.x * 256u)) {
-    const float depth = ds[i];
-    const bool m = mask_of(depth, ds[P + i], ds[2 * (size_t)P + i], gt_depth[i], extra_mask ? extra_mask[i] : 1.f);
-    const bool mc = (mode == 0) ? m : true;                  // mode 2: the colour sum runs over all pixels
-    g_ds[i] = gdepth(m, gt_depth[i], depth);
-    g_ds[P + i] = 0.f; g_ds[2 * (size_t)P + i] = 0.f;
-    if (mode != 1) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) g_im[(size_t)c * P + i] = gcol(mc, gt_im[(size_t)c * P + i], im[(size_t)c * P + i]);
-    }
-  }
+  });
 }
 
 // One band's share of the loss from its own sums and the sums over all bands ({sum_im, sum_depth, count, sum SSIM}): the
@@ -606,6 +504,101 @@ __global__ void band_share_kernel(const float* __restrict__ own, const float* __
 
 using namespace vtgs;
 
+// ---- host side: each kernel that several entry points launch is launched by one function here, on the rows [rb, re) or the
+// pixels [p0, p1) of the frame (the full-frame entry points: 0, H and 0, P) ---------------------------------------------------
+
+// what the loss entry points have in common: the mode, the four inputs, the frame size and the optional planes
+struct LossIn {
+  int32_t mode;
+  const float *im, *ds, *gt_im, *gt_depth;
+  int32_t H, W;
+  float sil_thres;
+  const float *extra_mask, *color_weight;                             // color_weight: the mapping loss's only (else NULL)
+  bool ok() const { return mode >= 0 && mode <= 2 && im && ds && gt_im && gt_depth && H > 0 && W > 0; }
+  float numel_im() const { return (float)((size_t)3 * H * W); }
+  float l1_coef() const { return color_weight ? 1.0f : 0.8f; }        // weighted: 10 additional_mask + 0.8 carries the 0.8
+};
+static LossIn loss_in(int32_t mode, const float* im, const float* ds, const float* gt_im, const float* gt_depth, int32_t H, int32_t W,
+                      float sil_thres, const float* extra_mask, const float* color_weight) {
+  return LossIn{mode, im, ds, gt_im, gt_depth, H, W, sil_thres, extra_mask, mode == 1 ? color_weight : nullptr};
+}
+
+// returns the rows of partial sums it writes
+static uint32_t launch_masked_l1(hipStream_t st, const LossIn& in, int32_t p0, int32_t p1, float* partial, float* g_im, float* g_ds) {
+  const uint32_t rows = vtgs_masked_l1_partial_rows(p1 - p0);
+  hipLaunchKernelGGL(masked_l1_kernel, dim3(rows), dim3(256), 0, st, in.im, in.ds, in.gt_im, in.gt_depth, in.H * in.W, in.sil_thres,
+                     in.mode, partial, g_im, g_ds, in.extra_mask, in.color_weight, p0, p1);
+  return rows;
+}
+
+// workgroups of an SSIM launch over `tiles` tiles: what the chip holds at once (256 CUs x 3 workgroups of 41 KB LDS), every
+// workgroup walking the same number of tiles when it can (ceil(tiles / rounds))
+static inline uint32_t ssim_grid(uint32_t tiles, uint32_t per_cu = 3u) {   // (the backward's 37 KB: 4 per CU)
+  const uint32_t kResident = 256u * per_cu;
+  if (tiles <= kResident) return tiles ? tiles : 1u;
+  const uint32_t rounds = (tiles + kResident - 1u) / kResident;
+  return (tiles + rounds - 1u) / rounds;
+}
+
+// the tile rows that cover the image rows [lo, hi)
+struct SsimRows { int tx, ty0, ty; };
+static SsimRows ssim_rows(int32_t W, int32_t lo, int32_t hi) { return SsimRows{(W + kST - 1) / kST, lo / kST, (hi - 1) / kST - lo / kST + 1}; }
+
+// SSIM sums (and derivative maps) of rows [rb, re); returns the rows of partial sums it writes
+static uint32_t launch_ssim_forward(hipStream_t st, const float* img1, const float* img2, int32_t C, int32_t H, int32_t W, int32_t rb,
+                                    int32_t re, float* partial, float* gmaps) {
+  const SsimRows t = ssim_rows(W, rb, re);
+  const uint32_t tiles = (uint32_t)(C * t.tx * t.ty);
+  hipLaunchKernelGGL(ssim_forward_kernel, dim3(ssim_grid(tiles)), dim3(256), 0, st, img1, img2, C, H, W, t.tx, t.ty, partial, gmaps,
+                     t.ty0, rb, re);
+  return tiles;
+}
+
+// the gradient of the SSIM of rows [rb, re): it lands on rows [rb - 5, re + 5) of the image
+static void launch_ssim_backward(hipStream_t st, const float* img1, const float* img2, const float* gmaps, const float* upstream,
+                                 int32_t C, int32_t H, int32_t W, int32_t rb, int32_t re, float* g_img1, float ssim_coef, float l1_coef,
+                                 const float* l1_weight) {
+  const SsimRows t = ssim_rows(W, rb - kSR > 0 ? rb - kSR : 0, re + kSR < H ? re + kSR : H);
+  hipLaunchKernelGGL(ssim_backward_kernel, dim3(ssim_grid((uint32_t)(C * t.tx * t.ty), 4u)), dim3(256), 0, st, img1, img2, gmaps,
+                     upstream, C, H, W, t.tx, t.ty, g_img1, ssim_coef, l1_coef, l1_weight, t.ty0, rb, re);
+}
+
+// the sums of rows [rb, re) into `scratch`: masked L1 partials first, the SSIM partials of the mapping loss behind the L1
+// partials of a whole frame (a band's too)
+struct LossSums { uint32_t l1_rows, ssim_rows; float* ssim_partial; };
+static LossSums launch_loss_sums(hipStream_t st, const LossIn& in, int32_t rb, int32_t re, float* scratch, float* ssim_grad_maps) {
+  LossSums s;
+  s.l1_rows = launch_masked_l1(st, in, rb * in.W, re * in.W, scratch, nullptr, nullptr);
+  s.ssim_partial = scratch + (size_t)vtgs_masked_l1_partial_rows(in.H * in.W) * 3;
+  s.ssim_rows = in.mode == 1 ? launch_ssim_forward(st, in.im, in.gt_im, 3, in.H, in.W, rb, re, s.ssim_partial, ssim_grad_maps) : 0u;
+  return s;
+}
+
+// both gradient images of rows [rb, re) (fwd_out: the out8 whose count the mapping depth term divides by)
+static void launch_loss_gradient(hipStream_t st, const LossIn& in, int32_t rb, int32_t re, float w_im, float w_depth,
+                                 const float* ssim_grad_maps, const float* fwd_out, const float* upstream, float* g_im, float* g_ds) {
+  const int32_t p0 = rb * in.W, p1 = re * in.W;
+  hipLaunchKernelGGL(loss_backward_kernel, dim3(vtgs_masked_l1_partial_rows(p1 - p0)), dim3(256), 0, st, in.im, in.ds, in.gt_im,
+                     in.gt_depth, in.H * in.W, in.sil_thres, in.mode, w_im, w_depth, upstream, fwd_out, g_im, g_ds, in.extra_mask, p0, p1);
+  if (in.mode == 1)
+    launch_ssim_backward(st, in.im, in.gt_im, ssim_grad_maps, upstream, 3, in.H, in.W, rb, re, g_im, -0.2f * w_im,
+                         in.l1_coef() * w_im / in.numel_im(), in.color_weight);
+}
+
+static int silhouette_sweep(const char* what, const float* im, const float* silhouette, const float* gt_im, const float* gt_depth,
+                            int32_t pixels, int32_t p0, int32_t p1, const float* thresholds, int32_t n_thresholds, float* partial_sums,
+                            void* stream) {
+  if (!im || !silhouette || !gt_im || !gt_depth || !thresholds || !partial_sums || pixels <= 0 || n_thresholds <= 0 ||
+      n_thresholds > 8 || p0 < 0 || p1 <= p0 || p1 > pixels)
+    return VTGS_ERR_INVALID_ARGUMENT;
+  SweepThresholds th;
+  th.n = n_thresholds;
+  for (int k = 0; k < 8; ++k) th.c[k] = k < n_thresholds ? thresholds[k] : 0.f;
+  hipLaunchKernelGGL(silhouette_sweep_kernel, dim3(vtgs_masked_l1_partial_rows(p1 - p0)), dim3(256), 0, (hipStream_t)stream, im,
+                     silhouette, gt_im, gt_depth, pixels, th, partial_sums, p0, p1);
+  return launch_status(what);
+}
+
 extern "C" {
 
 uint32_t vtgs_masked_l1_partial_rows(int32_t pixels) {
@@ -616,83 +609,22 @@ uint32_t vtgs_masked_l1_partial_rows(int32_t pixels) {
 
 int vtgs_masked_l1(const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth, int32_t pixels,
                    float sil_thres, int32_t mode, float* partial_sums, float* g_im, float* g_depth_sil, void* stream) {
-  if (!im || !depth_sil || !gt_im || !gt_depth || !partial_sums || !g_im || !g_depth_sil || pixels <= 0 || (mode < 0 || mode > 2))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(masked_l1_kernel, dim3(vtgs_masked_l1_partial_rows(pixels)), dim3(256), 0, (hipStream_t)stream, im,
-                     depth_sil, gt_im, gt_depth, pixels, sil_thres, mode, partial_sums, g_im, g_depth_sil);
+  const LossIn in = loss_in(mode, im, depth_sil, gt_im, gt_depth, 1, pixels, sil_thres, nullptr, nullptr);   // one row of pixels
+  if (!in.ok() || !partial_sums || !g_im || !g_depth_sil) return VTGS_ERR_INVALID_ARGUMENT;
+  launch_masked_l1((hipStream_t)stream, in, 0, pixels, partial_sums, g_im, g_depth_sil);
   return launch_status(__func__);
 }
 
 int vtgs_silhouette_sweep(const float* im, const float* silhouette, const float* gt_im, const float* gt_depth,
                           int32_t pixels, const float* thresholds, int32_t n_thresholds, float* partial_sums, void* stream) {
-  if (!im || !silhouette || !gt_im || !gt_depth || !thresholds || !partial_sums || pixels <= 0 || n_thresholds <= 0 ||
-      n_thresholds > 8)
-    return VTGS_ERR_INVALID_ARGUMENT;
-  SweepThresholds th;
-  th.n = n_thresholds;
-  for (int k = 0; k < 8; ++k) th.c[k] = k < n_thresholds ? thresholds[k] : 0.f;
-  hipLaunchKernelGGL(silhouette_sweep_kernel, dim3(vtgs_masked_l1_partial_rows(pixels)), dim3(256), 0, (hipStream_t)stream,
-                     im, silhouette, gt_im, gt_depth, pixels, th, partial_sums);
-  return launch_status(__func__);
+  return silhouette_sweep(__func__, im, silhouette, gt_im, gt_depth, pixels, 0, pixels, thresholds, n_thresholds, partial_sums, stream);
 }
 
-int vtgs_adam_step(const VtgsAdamGroup* groups, int32_t n_groups, int32_t step, float beta1, float beta2, void* stream) {
-  if (!groups || n_groups <= 0 || n_groups > VTGS_ADAM_MAX_GROUPS || step <= 0 || !(beta1 >= 0.f && beta1 < 1.f) ||
-      !(beta2 >= 0.f && beta2 < 1.f))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  AdamLaunch a;
-  uint64_t longest = 0;
-  for (int k = 0; k < VTGS_ADAM_MAX_GROUPS; ++k) {
-    if (k < n_groups) {
-      a.g[k] = groups[k];
-      if (a.g[k].count && (!a.g[k].param || !a.g[k].grad || !a.g[k].exp_avg || !a.g[k].exp_avg_sq)) return VTGS_ERR_INVALID_ARGUMENT;
-      longest = a.g[k].count > longest ? a.g[k].count : longest;
-    } else {
-      a.g[k] = VtgsAdamGroup{nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0.f};
-    }
-  }
-  if (longest == 0) return VTGS_OK;
-  if (longest > (uint64_t)0x7fffffff * 256u) return VTGS_ERR_INVALID_ARGUMENT;
-  a.step_size_scale = (float)(1.0 / (1.0 - pow((double)beta1, (double)step)));   // lr / bias_correction1
-  a.sqrt_bias2 = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  hipLaunchKernelGGL(adam_step_kernel, dim3((uint32_t)((longest + 1023) / 1024), (uint32_t)n_groups), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  return launch_status(__func__);
-}
-
-int vtgs_adam_step_rows(const VtgsAdamGroup* groups, int32_t n_groups, int32_t step, float beta1, float beta2,
-                        const int32_t* rows, int32_t n_rows, int32_t n_total_rows, void* stream) {
-  if (!groups || n_groups <= 0 || n_groups > VTGS_ADAM_MAX_GROUPS || step <= 0 || !(beta1 >= 0.f && beta1 < 1.f) ||
-      !(beta2 >= 0.f && beta2 < 1.f) || n_rows < 0 || n_total_rows <= 0 || (n_rows > 0 && !rows))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  AdamLaunch a;
-  AdamRows r;
-  r.rows = rows; r.n_rows = n_rows;
-  uint64_t longest = 0;
-  for (int k = 0; k < VTGS_ADAM_MAX_GROUPS; ++k) {
-    r.width[k] = 0u;
-    if (k < n_groups) {
-      a.g[k] = groups[k];
-      if (a.g[k].count % (uint64_t)n_total_rows) return VTGS_ERR_INVALID_ARGUMENT;
-      if (a.g[k].count && (!a.g[k].param || !a.g[k].grad || !a.g[k].exp_avg || !a.g[k].exp_avg_sq)) return VTGS_ERR_INVALID_ARGUMENT;
-      r.width[k] = (uint32_t)(a.g[k].count / (uint64_t)n_total_rows);
-      const uint64_t work = (uint64_t)n_rows * r.width[k];
-      longest = work > longest ? work : longest;
-    } else {
-      a.g[k] = VtgsAdamGroup{nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0.f};
-    }
-  }
-  if (longest == 0) return VTGS_OK;
-  if (longest > (uint64_t)0x7fffffff * 256u) return VTGS_ERR_INVALID_ARGUMENT;
-  a.step_size_scale = (float)(1.0 / (1.0 - pow((double)beta1, (double)step)));
-  a.sqrt_bias2 = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  hipLaunchKernelGGL(adam_step_rows_kernel, dim3((uint32_t)((longest + 255) / 256), (uint32_t)n_groups), dim3(256), 0,
-                     (hipStream_t)stream, a, r);
-  return launch_status(__func__);
+int vtgs_silhouette_sweep_band(const float* im, const float* silhouette, const float* gt_im, const float* gt_depth,
+                               int32_t pixels, int32_t pixel_begin, int32_t pixel_end, const float* thresholds,
+                               int32_t n_thresholds, float* partial_sums, void* stream) {
+  return silhouette_sweep(__func__, im, silhouette, gt_im, gt_depth, pixels, pixel_begin, pixel_end, thresholds, n_thresholds,
+                          partial_sums, stream);
 }
 
 // seen_and_max_radius_block has no scalar fallback: radii / max_2d_radius are read as int4 / float4 and four `seen` bytes are
@@ -710,15 +642,6 @@ int vtgs_seen_and_max_radius(int32_t n, const int32_t* radii, float* max_2d_radi
   return launch_status(__func__);
 }
 
-// workgroups of an SSIM launch over `tiles` tiles: what the chip holds at once (256 CUs x 3 workgroups of 41 KB LDS), every
-// workgroup walking the same number of tiles when it can (ceil(tiles / rounds))
-static inline uint32_t ssim_grid(uint32_t tiles, uint32_t per_cu = 3u) {   // (the backward's 37 KB: 4 per CU)
-  const uint32_t kResident = 256u * per_cu;
-  if (tiles <= kResident) return tiles ? tiles : 1u;
-  const uint32_t rounds = (tiles + kResident - 1u) / kResident;
-  return (tiles + rounds - 1u) / rounds;
-}
-
 uint32_t vtgs_ssim_partial_rows(int32_t channels, int32_t height, int32_t width) {
   if (channels <= 0 || height <= 0 || width <= 0) return 0;
   return (uint32_t)(channels * ((height + kST - 1) / kST) * ((width + kST - 1) / kST));
@@ -727,9 +650,7 @@ uint32_t vtgs_ssim_partial_rows(int32_t channels, int32_t height, int32_t width)
 int vtgs_ssim_forward(const float* img1, const float* img2, int32_t channels, int32_t height, int32_t width,
                       float* partial_sums, float* grad_maps, void* stream) {
   if (!img1 || !img2 || !partial_sums || channels <= 0 || height <= 0 || width <= 0) return VTGS_ERR_INVALID_ARGUMENT;
-  const int tx = (width + kST - 1) / kST, ty = (height + kST - 1) / kST;
-  hipLaunchKernelGGL(ssim_forward_kernel, dim3(ssim_grid((uint32_t)(channels * tx * ty))), dim3(256), 0, (hipStream_t)stream, img1, img2, channels,
-                     height, width, tx, ty, partial_sums, grad_maps);
+  launch_ssim_forward((hipStream_t)stream, img1, img2, channels, height, width, 0, height, partial_sums, grad_maps);
   return launch_status(__func__);
 }
 
@@ -737,9 +658,8 @@ int vtgs_ssim_backward(const float* img1, const float* img2, const float* grad_m
                        int32_t channels, int32_t height, int32_t width, float* grad_img1, void* stream) {
   if (!img1 || !img2 || !grad_maps || !upstream || !grad_img1 || channels <= 0 || height <= 0 || width <= 0)
     return VTGS_ERR_INVALID_ARGUMENT;
-  const int tx = (width + kST - 1) / kST, ty = (height + kST - 1) / kST;
-  hipLaunchKernelGGL(ssim_backward_kernel, dim3(ssim_grid((uint32_t)(channels * tx * ty), 4u)), dim3(256), 0, (hipStream_t)stream, img1, img2, grad_maps,
-                     upstream, channels, height, width, tx, ty, grad_img1, 1.f, 0.f);
+  launch_ssim_backward((hipStream_t)stream, img1, img2, grad_maps, upstream, channels, height, width, 0, height, grad_img1, 1.f, 0.f,
+                       nullptr);
   return launch_status(__func__);
 }
 
@@ -748,6 +668,7 @@ size_t vtgs_loss_scratch_floats(int32_t height, int32_t width) {
   return (size_t)vtgs_masked_l1_partial_rows(height * width) * 3 + vtgs_ssim_partial_rows(3, height, width);
 }
 
+// ---- whole loss of get_loss in a handful of launches (see loss_finalize_kernel) ---------------------------------------------
 int vtgs_slam_loss_forward(int32_t mode, const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth,
                            int32_t height, int32_t width, float sil_thres, float w_im, float w_depth, float* scratch,
                            float* ssim_grad_maps, float* out5, const float* extra_mask, const float* color_weight,
@@ -760,26 +681,15 @@ int vtgs_slam_loss_forward_seen(int32_t mode, const float* im, const float* dept
                                 int32_t height, int32_t width, float sil_thres, float w_im, float w_depth, float* scratch,
                                 float* ssim_grad_maps, float* out5, const float* extra_mask, const float* color_weight,
                                 int32_t n, const int32_t* radii, float* max_2d_radius, uint8_t* seen, void* stream) {
-  if ((mode < 0 || mode > 2) || !im || !depth_sil || !gt_im || !gt_depth || !scratch || !out5 || height <= 0 || width <= 0)
-    return VTGS_ERR_INVALID_ARGUMENT;
+  const LossIn in = loss_in(mode, im, depth_sil, gt_im, gt_depth, height, width, sil_thres, extra_mask, color_weight);
+  if (!in.ok() || !scratch || !out5) return VTGS_ERR_INVALID_ARGUMENT;
   if (n < 0 || (n > 0 && (!radii || !max_2d_radius || !seen))) return VTGS_ERR_INVALID_ARGUMENT;
   if (n > 0 && !bookkeeping_aligned(radii, max_2d_radius, seen)) return VTGS_ERR_INVALID_ARGUMENT;
-  const int32_t P = height * width;
-  const uint32_t l1_rows = vtgs_masked_l1_partial_rows(P);
-  float* ssim_partial = scratch + (size_t)l1_rows * 3;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(masked_l1_kernel, dim3(l1_rows), dim3(256), 0, st, im, depth_sil, gt_im, gt_depth, P, sil_thres, mode,
-                     scratch, (float*)nullptr, (float*)nullptr, extra_mask, mode == 1 ? color_weight : (const float*)nullptr);
-  uint32_t ssim_rows = 0;
-  if (mode == 1) {
-    const int tx = (width + kST - 1) / kST, ty = (height + kST - 1) / kST;
-    ssim_rows = (uint32_t)(3 * tx * ty);
-    hipLaunchKernelGGL(ssim_forward_kernel, dim3(ssim_grid((uint32_t)(ssim_rows))), dim3(256), 0, st, im, gt_im, 3, height, width, tx, ty,
-                       ssim_partial, ssim_grad_maps);
-  }
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1u + (uint32_t)((n + 1023) / 1024)), dim3(256), 0, st, scratch, l1_rows, ssim_partial,
-                     ssim_rows, mode, w_im, w_depth, (float)((size_t)3 * P), out5, (mode == 1 && color_weight) ? 1.0f : 0.8f, 0,
-                     (int)n, radii, max_2d_radius, seen);
+  const LossSums s = launch_loss_sums(st, in, 0, height, scratch, ssim_grad_maps);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1u + (uint32_t)((n + 1023) / 1024)), dim3(256), 0, st, scratch, s.l1_rows,
+                     s.ssim_partial, s.ssim_rows, mode, w_im, w_depth, in.numel_im(), out5, in.l1_coef(), 0, (int)n, radii,
+                     max_2d_radius, seen);
   return launch_status(__func__);
 }
 
@@ -787,50 +697,25 @@ int vtgs_slam_loss_backward(int32_t mode, const float* im, const float* depth_si
                             int32_t height, int32_t width, float sil_thres, float w_im, float w_depth,
                             const float* ssim_grad_maps, const float* fwd_out5, const float* upstream, float* g_im,
                             float* g_depth_sil, const float* extra_mask, const float* color_weight, void* stream) {
-  if ((mode < 0 || mode > 2) || !im || !depth_sil || !gt_im || !gt_depth || !fwd_out5 || !upstream || !g_im || !g_depth_sil ||
-      height <= 0 || width <= 0 || (mode == 1 && !ssim_grad_maps))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  const int32_t P = height * width;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(loss_backward_kernel, dim3(vtgs_masked_l1_partial_rows(P)), dim3(256), 0, st, im, depth_sil, gt_im,
-                     gt_depth, P, sil_thres, mode, w_im, w_depth, upstream, fwd_out5, g_im, g_depth_sil, extra_mask);
-  if (mode == 1) {
-    const int tx = (width + kST - 1) / kST, ty = (height + kST - 1) / kST;
-    hipLaunchKernelGGL(ssim_backward_kernel, dim3(ssim_grid((uint32_t)(3 * tx * ty), 4u)), dim3(256), 0, st, im, gt_im, ssim_grad_maps, upstream, 3,
-                       height, width, tx, ty, g_im, -0.2f * w_im, (color_weight ? 1.0f : 0.8f) * w_im / (float)((size_t)3 * P),
-                       color_weight);
-  }
+  const LossIn in = loss_in(mode, im, depth_sil, gt_im, gt_depth, height, width, sil_thres, extra_mask, color_weight);
+  if (!in.ok() || !fwd_out5 || !upstream || !g_im || !g_depth_sil || (mode == 1 && !ssim_grad_maps)) return VTGS_ERR_INVALID_ARGUMENT;
+  launch_loss_gradient((hipStream_t)stream, in, 0, height, w_im, w_depth, ssim_grad_maps, fwd_out5, upstream, g_im, g_depth_sil);
   return launch_status(__func__);
 }
 
 // ---- one band of the tile-row partition: additive sums, the band's share, its gradient images -----------
-static bool band_ok(int32_t height, int32_t width, int32_t rb, int32_t re) {
-  return height > 0 && width > 0 && rb >= 0 && re > rb && re <= height;
-}
+static bool band_ok(int32_t height, int32_t rb, int32_t re) { return rb >= 0 && re > rb && re <= height; }
 
 int vtgs_slam_loss_band_sums(int32_t mode, const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth,
                              int32_t height, int32_t width, int32_t row_begin, int32_t row_end, float sil_thres,
                              float* scratch, float* ssim_grad_maps, float* sums8, const float* extra_mask,
                              const float* color_weight, void* stream) {
-  if ((mode < 0 || mode > 2) || !im || !depth_sil || !gt_im || !gt_depth || !scratch || !sums8 ||
-      !band_ok(height, width, row_begin, row_end))
-    return VTGS_ERR_INVALID_ARGUMENT;
-  const int32_t P = height * width, p0 = row_begin * width, p1 = row_end * width;
-  const uint32_t l1_rows = vtgs_masked_l1_partial_rows(p1 - p0);
-  float* ssim_partial = scratch + (size_t)vtgs_masked_l1_partial_rows(P) * 3;
+  const LossIn in = loss_in(mode, im, depth_sil, gt_im, gt_depth, height, width, sil_thres, extra_mask, color_weight);
+  if (!in.ok() || !scratch || !sums8 || !band_ok(height, row_begin, row_end)) return VTGS_ERR_INVALID_ARGUMENT;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(masked_l1_kernel, dim3(l1_rows), dim3(256), 0, st, im, depth_sil, gt_im, gt_depth, P, sil_thres, mode,
-                     scratch, (float*)nullptr, (float*)nullptr, extra_mask, mode == 1 ? color_weight : (const float*)nullptr,
-                     p0, p1);
-  uint32_t ssim_rows = 0;
-  if (mode == 1) {
-    const int tx = (width + kST - 1) / kST, ty0 = row_begin / kST, ty = (row_end - 1) / kST - ty0 + 1;
-    ssim_rows = (uint32_t)(3 * tx * ty);
-    hipLaunchKernelGGL(ssim_forward_kernel, dim3(ssim_grid((uint32_t)(ssim_rows))), dim3(256), 0, st, im, gt_im, 3, height, width, tx, ty,
-                       ssim_partial, ssim_grad_maps, ty0, row_begin, row_end);
-  }
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, l1_rows, ssim_partial, ssim_rows, mode, 0.f,
-                     0.f, (float)((size_t)3 * P), sums8, 0.8f, 1);
+  const LossSums s = launch_loss_sums(st, in, row_begin, row_end, scratch, ssim_grad_maps);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, s.l1_rows, s.ssim_partial, s.ssim_rows, mode, 0.f,
+                     0.f, in.numel_im(), sums8, 0.8f, 1);
   return launch_status(__func__);
 }
 
@@ -848,35 +733,14 @@ int vtgs_slam_loss_band_backward(int32_t mode, const float* im, const float* dep
                                  float sil_thres, float w_im, float w_depth, const float* ssim_grad_maps,
                                  const float* share_out8, const float* upstream, float* g_im, float* g_depth_sil,
                                  const float* extra_mask, const float* color_weight, void* stream) {
-  if ((mode < 0 || mode > 2) || !im || !depth_sil || !gt_im || !gt_depth || !share_out8 || !upstream || !g_im || !g_depth_sil ||
-      !band_ok(height, width, row_begin, row_end) || (mode == 1 && !ssim_grad_maps))
+  const LossIn in = loss_in(mode, im, depth_sil, gt_im, gt_depth, height, width, sil_thres, extra_mask, color_weight);
+  if (!in.ok() || !share_out8 || !upstream || !g_im || !g_depth_sil || !band_ok(height, row_begin, row_end) ||
+      (mode == 1 && !ssim_grad_maps))
     return VTGS_ERR_INVALID_ARGUMENT;
-  const int32_t P = height * width, p0 = row_begin * width, p1 = row_end * width;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(loss_backward_kernel, dim3(vtgs_masked_l1_partial_rows(p1 - p0)), dim3(256), 0, st, im, depth_sil, gt_im,
-                     gt_depth, P, sil_thres, mode, w_im, w_depth, upstream, share_out8, g_im, g_depth_sil, extra_mask, p0, p1);
-  if (mode == 1) {
-    const int lo = row_begin - kSR > 0 ? row_begin - kSR : 0, hi = row_end + kSR < height ? row_end + kSR : height;
-    const int tx = (width + kST - 1) / kST, ty0 = lo / kST, ty = (hi - 1) / kST - ty0 + 1;
-    hipLaunchKernelGGL(ssim_backward_kernel, dim3(ssim_grid((uint32_t)(3 * tx * ty), 4u)), dim3(256), 0, st, im, gt_im, ssim_grad_maps, upstream, 3,
-                       height, width, tx, ty, g_im, -0.2f * w_im, (color_weight ? 1.0f : 0.8f) * w_im / (float)((size_t)3 * P),
-                       color_weight, ty0, row_begin, row_end);
-  }
-  return launch_status(__func__);
-}
-
-int vtgs_silhouette_sweep_band(const float* im, const float* silhouette, const float* gt_im, const float* gt_depth,
-                               int32_t pixels, int32_t pixel_begin, int32_t pixel_end, const float* thresholds,
-                               int32_t n_thresholds, float* partial_sums, void* stream) {
-  if (!im || !silhouette || !gt_im || !gt_depth || !thresholds || !partial_sums || pixels <= 0 || n_thresholds <= 0 ||
-      n_thresholds > 8 || pixel_begin < 0 || pixel_end <= pixel_begin || pixel_end > pixels)
-    return VTGS_ERR_INVALID_ARGUMENT;
-  SweepThresholds th;
-  th.n = n_thresholds;
-  for (int k = 0; k < 8; ++k) th.c[k] = k < n_thresholds ? thresholds[k] : 0.f;
-  hipLaunchKernelGGL(silhouette_sweep_kernel, dim3(vtgs_masked_l1_partial_rows(pixel_end - pixel_begin)), dim3(256), 0,
-                     (hipStream_t)stream, im, silhouette, gt_im, gt_depth, pixels, th, partial_sums, pixel_begin, pixel_end);
+  launch_loss_gradient((hipStream_t)stream, in, row_begin, row_end, w_im, w_depth, ssim_grad_maps, share_out8, upstream, g_im,
+                       g_depth_sil);
   return launch_status(__func__);
 }
 
 }  // extern "C"
+
